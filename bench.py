@@ -7,7 +7,9 @@ context update, T times) of `--batch` synthetic episodes per GPU, inputs residen
 Multi-GPU: episodes are independent, every rank rolls out its own batch (weak scaling, no
 data-path collective in the forward rollout); value = all ranks' designs / max-over-ranks time.
 
-    python bench.py                       # 1 GPU, defaults finish in a few minutes
+    python bench.py                       # 1 GPU: set-up, warm-up, the timed steps, one JSON result line
+    python bench.py --full                # the same, then every secondary measurement (a few minutes)
+    python bench.py --dump-outputs DIR    # also write what the last timed step computed as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -447,6 +449,26 @@ def rollout_ms_with_query_gmm(args, model, batch, device):
     return (time.perf_counter() - t0) / args.steps * 1e3, ro.path
 
 
+DUMP_LIMIT_BYTES = 64 << 20            # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(ro, out_dir):
+    """--dump-outputs: what the caller of the last timed rollout receives (the chosen designs, their log-probabilities, the targets'
+    log-likelihoods and the GMM posterior of every step), one `<name>.npy` each: float32, the int64 design indices as float64.  An
+    array above its share of DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its elements (sorted flat positions)."""
+    import numpy as np
+    arrays = {k: getattr(ro, k) for k in ("idx", "log_prob", "target_ll", "post_mean", "post_std", "post_weight")
+              if getattr(ro, k) is not None}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        a = a.detach().double() if a.dtype == torch.int64 else a.detach().float()
+        cap = DUMP_LIMIT_BYTES // len(arrays) // a.element_size()
+        if a.numel() > cap:
+            pos = np.sort(np.random.default_rng(0).integers(0, a.numel(), cap))
+            a = a.reshape(-1)[torch.from_numpy(pos).to(a.device)]
+        np.save(os.path.join(out_dir, k + ".npy"), a.cpu().numpy())
+
+
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
@@ -482,7 +504,16 @@ def main():
     ap.add_argument("--no-eig", action="store_true", help="skip the sequential-EIG kernels' HBM-roofline sub-measurement (N = 1 only)")
     ap.add_argument("--no-query-gmm", action="store_true", help="skip the value_with_query_gmm figure")
     ap.add_argument("--d256-precs", default="f16x3", help="arithmetic modes of the d_model = 256 sub-measurement (comma separated)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every secondary measurement as well: the sustained leg, the dominant kernel's roofline, "
+                         "the training step, the query GMM, the f32 / d_model = 256 / d_model = 512 legs, the EIG kernels and the CPU "
+                         "baseline (each with its own switch above).  Without it none of them runs, whatever their switches say")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed rollout as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if not args.full:                   # a plain run: set-up, warm-up, the timed steps, the result line
+        args.sustain_s, args.train_steps = 0.0, 0
+        args.no_query_gmm = args.no_f32 = args.no_d256 = args.no_d512 = args.no_eig = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `bench.py --gpus N` without a launcher: start the N ranks here, BEFORE anything touches the GPU (a process that
@@ -574,6 +605,7 @@ def main():
     for _ in range(args.warmup):
         ro.refresh_uniform()
         run()
+    torch.manual_seed(args.seed + rank + 1000)      # the timed steps draw the same uniforms in every run, however many rollouts the pre-warm fitted in
     barrier()
     log("warm-up done; timing ...")
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -589,6 +621,9 @@ def main():
     designs_per_rollout = args.batch * args.T * args.n_query
     # whole job = the designs of all ranks / the slowest rank's time
     value, dt, _ = aggregate_throughput(float(designs_per_rollout * args.steps), dt, dist, device, always=force_dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ro, args.dump_outputs)
+        log(f"outputs of the last timed rollout written to {args.dump_outputs}")
 
     # sustained leg: the same replay back to back for >= --sustain-s seconds (so that SMI sampling sees the GPU busy)
     sustained_ms = None
@@ -610,7 +645,7 @@ def main():
     # kernel, in an eager leg of the same process right after the timed region (same inputs, same
     # launches; the graph replays above launch exactly this kernel)
     path = ro.path
-    per_step = dominant_kernel_ms(ro, device) if path != "generic pipeline" else {}
+    per_step = dominant_kernel_ms(ro, device) if args.full and path != "generic pipeline" else {}
     if path == "fused::rollout_f32_kernel" and per_step:      # (one launch per rollout: every "step" timed the same launch)
         per_step = {0: sum(per_step.values()) / len(per_step)}
     kernel_ms = sum(per_step.values()) / len(per_step) if per_step else 0.0
@@ -724,6 +759,8 @@ def main():
                      "device_ms_per_rollout": dev_ms / args.steps,
                      **extra},
     }
+    if not args.full:                   # (the dominant kernel was not timed: no roofline figure in a plain run)
+        del out["roofline"]
     log(f"timed region done: {dt / args.steps * 1e3:.2f} ms per rollout")
     if args.train_steps > 0 and args.precision in ("f32", "f16x3"):
         # secondary measurement (not `value`): one optimiser step of train_aline.py:55-152 -- sampled

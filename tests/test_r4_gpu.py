@@ -132,7 +132,7 @@ def test_bench_runs_its_rccl_branch_in_a_world_of_one():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ALINE_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "64", "--steps", "2", "--warmup", "1",
-                          "--train-steps", "1", "--sustain-s", "0", "--prewarm-s", "0", "--no-d256", "--no-d512", "--no-f32",
+                          "--full", "--train-steps", "1", "--sustain-s", "0", "--prewarm-s", "0", "--no-d256", "--no-d512", "--no-f32",
                           "--no-query-gmm", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -140,6 +140,41 @@ def test_bench_runs_its_rccl_branch_in_a_world_of_one():
     j = json.loads(lines[0])
     assert j["n_gpus"] == 1 and j["config"]["backend"] == "nccl" and j["config"]["forced_world_of_one"] is True
     assert j["train_step"]["rccl_allreduce_per_step"] == 1.0 and j["train_step"]["collective"].startswith("1 all-reduce")
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times its steps and prints the headline line only -- no secondary leg, whatever their
+    switches say -- and `--dump-outputs DIR` writes what the last timed rollout returned: float32 / float64 arrays of the rollout's
+    shapes, finite, the design indices within the candidate set."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    B, T, nq = 64, 5, 40
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", str(B), "--T", str(T), "--n-query", str(nq),
+                          "--steps", "3", "--warmup", "1", "--prewarm-s", "0", "--train-steps", "1", "--dump-outputs", str(tmp_path / "dump")],
+                         env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "designs/s" and j["higher_is_better"] is True
+    assert abs(j["value"] - B * T * nq / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+    for k in ("roofline", "train_step", "value_with_query_gmm", "f32", "d256", "d512", "eig", "cpu_baseline"):
+        assert k not in j, k
+    assert j["sustained_ms_per_step"] is None
+    shapes = {"idx": (B, T), "log_prob": (B, T), "target_ll": (T, B, 2), "post_mean": (T, B, 2, 10), "post_std": (T, B, 2, 10),
+              "post_weight": (T, B, 2, 10)}
+    assert sorted(os.listdir(tmp_path / "dump")) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a = np.load(tmp_path / "dump" / (k + ".npy"))
+        assert a.shape == shape and a.dtype == (np.float64 if k == "idx" else np.float32) and np.isfinite(a).all(), k
+    idx = np.load(tmp_path / "dump" / "idx.npy")
+    assert (idx == np.round(idx)).all() and idx.min() >= 0 and (idx < nq - np.arange(T)).all()     # positions in the remaining candidates
+    assert np.allclose(np.load(tmp_path / "dump" / "post_weight.npy").sum(-1), 1.0, atol=1e-5)
 
 
 @pytest.mark.parametrize("B,L,T,K", [(200, 120_000, 31, 1), (20, 300_000, 11, 1), (7, 5_000, 36, 1), (33, 20_000, 6, 2)])
