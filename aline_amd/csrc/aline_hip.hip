@@ -641,34 +641,44 @@ static int launch_s3_step(const Ctx &c, const S3Shape &sh, const s3::StepArgs &a
     default: return ALINE_EUNSUPPORTED;
   }
 }
-// the x rows and the y rows of a rollout in ONE launch (two were 2 x 42 us at the headline shape, most of it ramp: each workgroup packs its W2 pairs first)
+// the x rows, the y rows and the X0 image of a rollout in ONE launch.  Every workgroup first loads the two embedder images (42 KB at
+// F = 128): a wave gets at least four tiles before workgroups are added, and no more than the two workgroups a CU holds (~180 registers) walk the tiles
 template <int F>
-static int launch_s3_embed_f(const Ctx &c, const s3::EmbArgs &a, const s3::EmbArgs &b) {
-  const long ta = ((long)a.B * a.rows_per_ep + 15) / 16, tb = ((long)b.B * b.rows_per_ep + 15) / 16;
-  // (every workgroup first packs the W2 fragment pairs into LDS: a few workgroups per CU that walk the tiles, not one per 4 tiles)
-  const long cap = 2L * device_cus();
-  const unsigned na = (unsigned)std::max<long>(1, std::min<long>((ta + 3) / 4, cap)), nb = (unsigned)std::max<long>(1, std::min<long>((tb + 3) / 4, cap));
-  hipLaunchKernelGGL(s3::embed_kernel<F>, dim3(na + nb), dim3(256), 0, c.st, a, b, na);
+static int launch_s3_embed_f(const Ctx &c, const s3::EmbArgs &a) {
+  const long ntiles = ((long)a.B * (a.P + a.n_td) + 15) / 16, per_wg = 4L * s3::EMB_WAVES;
+  const unsigned nwg = (unsigned)std::max<long>(1, std::min<long>((ntiles + per_wg - 1) / per_wg, 2L * device_cus()));
+  hipLaunchKernelGGL(s3::embed_kernel<F>, dim3(nwg), dim3(s3::EMB_WAVES * 64), 0, c.st, a);
   CHECK_LAUNCH();
   return ALINE_OK;
 }
-static int launch_s3_embed(const Ctx &c, int F, const s3::EmbArgs &a, const s3::EmbArgs &b) {
+static int launch_s3_embed(const Ctx &c, int F, const s3::EmbArgs &a) {
   switch (F) {
-    case 32: return launch_s3_embed_f<32>(c, a, b);
-    case 64: return launch_s3_embed_f<64>(c, a, b);
-    case 96: return launch_s3_embed_f<96>(c, a, b);
-    case 128: return launch_s3_embed_f<128>(c, a, b);
+    case 32: return launch_s3_embed_f<32>(c, a);
+    case 64: return launch_s3_embed_f<64>(c, a);
+    case 96: return launch_s3_embed_f<96>(c, a);
+    case 128: return launch_s3_embed_f<128>(c, a);
     default: return ALINE_EUNSUPPORTED;
   }
 }
-template <int F>
-static int launch_s3_gmm_f(const Ctx &c, const s3::GmmArgs &a) {
-  const size_t smem = (size_t)s3::head_bytes(F) + (size_t)3 * a.C * s3::GROWS * sizeof(float);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&s3::gmm_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  const long per_wg = (long)s3::WAVES * s3::GT;
-  hipLaunchKernelGGL(s3::gmm_kernel<F>, dim3((unsigned)((a.ntiles + per_wg - 1) / per_wg)), dim3(s3::THREADS), smem, c.st, a);
+// tiles per wave of the GMM kernel: two (the headline's 3750 target-row tiles: 235 workgroups on 256 CUs; 70 KB of LDS: two workgroups
+// share a CU when there are more), one when even that leaves CUs without a workgroup.  Four tiles per wave (100 KB: one workgroup
+// per CU) measured 4 % slower on the 6 M candidate rows of posterior_out_query.  ALINE_DBG_S3_GMM_GT forces either.
+static int gmm_tiles_per_wave(long ntiles) {
+  if (const int gt = dbg_param(ALINE_DBG_S3_GMM_GT)) return gt >= 2 ? 2 : 1;
+  return ntiles >= 2L * device_cus() * s3::WAVES ? 2 : 1;
+}
+template <int F, int GT>
+static int launch_s3_gmm_v(const Ctx &c, const s3::GmmArgs &a) {
+  const size_t smem = (size_t)s3::gmm_lds_bytes(F, a.C, GT);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&s3::gmm_kernel<F, GT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  const long per_wg = (long)s3::WAVES * GT;
+  hipLaunchKernelGGL((s3::gmm_kernel<F, GT>), dim3((unsigned)((a.ntiles + per_wg - 1) / per_wg)), dim3(s3::THREADS), smem, c.st, a);
   CHECK_LAUNCH();
   return ALINE_OK;
+}
+template <int F>
+static int launch_s3_gmm_f(const Ctx &c, const s3::GmmArgs &a) {
+  return gmm_tiles_per_wave(a.ntiles) == 2 ? launch_s3_gmm_v<F, 2>(c, a) : launch_s3_gmm_v<F, 1>(c, a);
 }
 static int launch_s3_gmm(const Ctx &c, int F, const s3::GmmArgs &a) {
   switch (F) {
@@ -946,11 +956,28 @@ static int rollout_s3(const aline_model *m, const aline_rollout *r, void *ws, si
   Ctx c;
   TRY(rollout_ctx(m, r, ws, ws_bytes, stream, c));
   TRY(check_select(r->select_mode, r->uniform, r->forced_idx));
-  TRY(c.clear_flag());
   const int n_t = c.g.n_td + c.g.n_th, N = c.g.N, F = m->F, tpe = (N + 15) / 16, NP = 16 * tpe;
-  const long tiles = (long)r->B * tpe;
   using s3::u32x4;
-  hipLaunchKernelGGL(role_init_kernel, grid1d((size_t)r->B * r->P), dim3(256), 0, c.st, r->role, r->B, r->P, r->n_ctx0);
+  const S3Shape sh = s3_shape(*m, *r);
+  u32x4 *X0 = reinterpret_cast<u32x4 *>(c.at(c.pl.sX0)), *XW = reinterpret_cast<u32x4 *>(c.at(c.pl.sXW));
+  u32x4 *Zimg = reinterpret_cast<u32x4 *>(c.at(c.pl.sZimg));
+  float *logits = c.at(c.pl.sLog);
+  const int zw = r->P - r->n_ctx0;
+  // ONE set-up launch (s3::setup_kernel): the range flag cleared, the roles initialised, the T argument sets of the in-kernel selections.
+  // It raises no flag itself, and the kernels that can -- pack_kernel first -- are later launches on the stream, so the clear still
+  // precedes every raiser.  (pack_kernel stays a launch of its own for that reason: pair_word raises the flag.)
+  // in-kernel selection: the argument sets live where the logits of the launch of its own would (they stay in LDS)
+  s3::SelArgs *selp = nullptr;
+  s3::SelArgs q{};
+  if (sh.sel && (size_t)r->T * sizeof(s3::SelArgs) <= (size_t)r->B * tpe * 16 * sizeof(float)) {
+    selp = reinterpret_cast<s3::SelArgs *>(logits);
+    q.on = 1; q.mode = r->select_mode; q.uniform = r->uniform;
+    q.forced = r->forced_idx; q.forced_stride = r->T;
+    q.idx = r->idx; q.idx_stride = r->T; q.slot = r->slot; q.slot_stride = r->T; q.log_prob = r->log_prob; q.lp_stride = r->T;
+    q.zt = r->zt; q.zt_stride = zw; q.zt_width = zw; q.role_out = r->role; q.range_flag = c.flag();
+  }
+  hipLaunchKernelGGL(s3::setup_kernel, grid1d(std::max<size_t>((size_t)r->B * r->P, 16)), dim3(256), 0, c.st, c.flag(), r->role, (long)r->B,
+                     (int)r->P, (int)r->n_ctx0, q, (int)r->T, selp);
   CHECK_LAUNCH();
   s3::PackArgs pa{};
   pa.L = m->L; pa.F = F; pa.C = m->C;
@@ -964,48 +991,25 @@ static int rollout_s3(const aline_model *m, const aline_rollout *r, void *ws, si
   }
   pa.acq_w1 = m->acq_w1; pa.acq_b1 = m->acq_b1; pa.acq_w2 = m->acq_w2; pa.acq_b2 = m->acq_b2;
   for (int k = 0; k < m->C; ++k) { pa.gmm_w1[k] = m->gmm_w1[k]; pa.gmm_b1[k] = m->gmm_b1[k]; pa.gmm_w2[k] = m->gmm_w2[k]; pa.gmm_b2[k] = m->gmm_b2[k]; }
+  pa.emb_w1[0] = m->x_w1; pa.emb_b1[0] = m->x_b1; pa.emb_w2[0] = m->x_w2; pa.emb_b2[0] = m->x_b2; pa.emb_K[0] = m->dim_x;
+  pa.emb_w1[1] = m->y_w1; pa.emb_b1[1] = m->y_b1; pa.emb_w2[1] = m->y_w2; pa.emb_b2[1] = m->y_b2; pa.emb_K[1] = m->dim_y;
   unsigned *img = reinterpret_cast<unsigned *>(c.at(c.pl.sImg));
   pa.out = img; pa.range_flag = c.flag(); pa.time_token = m->time_token ? 1 : 0;
   hipLaunchKernelGGL(s3::pack_kernel, dim3(256), dim3(256), 0, c.st, pa);
   CHECK_LAUNCH();
-  {   // step-invariant point embeddings (fp32 rows): x-embedder on the points + target-data rows, y-embedder on the points
-    s3::EmbArgs ex{};
-    ex.src = Src3{{r->point_x, r->target_x, nullptr}, {r->P, r->n_target_data, 0}};
-    ex.rows_per_ep = r->P + r->n_target_data; ex.B = r->B; ex.K = m->dim_x;
-    ex.w1 = m->x_w1; ex.b1 = m->x_b1; ex.w2 = m->x_w2; ex.b2 = m->x_b2; ex.E = c.at(c.pl.Ex); ex.range_flag = c.flag();
-    s3::EmbArgs ey{};
-    ey.src = Src3{{r->point_y, nullptr, nullptr}, {r->P, 0, 0}};
-    ey.rows_per_ep = r->P; ey.B = r->B; ey.K = m->dim_y;
-    ey.w1 = m->y_w1; ey.b1 = m->y_b1; ey.w2 = m->y_w2; ey.b2 = m->y_b2; ey.E = c.at(c.pl.Ey); ey.range_flag = c.flag();
-    if (dbg(ALINE_DBG_S3_GENERIC_EMBED)) {       // (A/B: the generic hidden-layer kernel + GEMM pair)
-      TRY(do_embed_points(c, ex.src, r->point_y, r->P));
-    } else {
-      TRY(launch_s3_embed(c, F, ex, ey));
-    }
+  {   // step-invariant point embeddings (fp32 rows: x-embedder on the points + target-data rows, y-embedder on the points) and the X0 image of step 0
+    s3::EmbArgs ea{};
+    ea.px = r->point_x; ea.tx = r->target_x; ea.py = r->point_y;
+    ea.B = r->B; ea.P = r->P; ea.n_td = r->n_target_data; ea.Kx = m->dim_x; ea.Ky = m->dim_y;
+    ea.n_ctx0 = r->n_ctx0; ea.N = N; ea.tpe = tpe;
+    ea.img = img + s3::emb_offset_words(m->L, F, m->C);
+    ea.Ex = c.at(c.pl.Ex); ea.Ey = c.at(c.pl.Ey); ea.theta_tokens = m->theta_tokens; ea.X0 = X0; ea.range_flag = c.flag();
+    TRY(launch_s3_embed(c, F, ea));
   }
-  u32x4 *X0 = reinterpret_cast<u32x4 *>(c.at(c.pl.sX0)), *XW = reinterpret_cast<u32x4 *>(c.at(c.pl.sXW));
-  u32x4 *Zimg = reinterpret_cast<u32x4 *>(c.at(c.pl.sZimg));
-  float *logits = c.at(c.pl.sLog);
-  s3::AsmArgs aa{};
+  s3::AsmArgs aa{};      // (the step kernel re-assembles the row of the point chosen at the previous step)
   aa.g = c.g; aa.tpe = tpe; aa.Ex = c.at(c.pl.Ex); aa.Ey = c.at(c.pl.Ey); aa.ey_rows = r->P; aa.theta_tokens = m->theta_tokens; aa.X = X0; aa.range_flag = c.flag();
-  hipLaunchKernelGGL(s3::assemble_kernel, grid1d((size_t)tiles * 64), dim3(256), 0, c.st, aa);
-  CHECK_LAUNCH();
   const bool want_gmm = r->post_mean || r->post_std || r->post_weight || r->target_ll;
-  const S3Shape sh = s3_shape(*m, *r);
   u32x4 *Zq = wants_postq(*r) ? reinterpret_cast<u32x4 *>(c.at(c.pl.sZq)) : nullptr;   // candidate rows of all steps
-  const int zw = r->P - r->n_ctx0;
-  // in-kernel selection: the T argument sets live where the logits of the launch of its own would (they stay in LDS)
-  s3::SelArgs *selp = nullptr;
-  if (sh.sel && (size_t)r->T * sizeof(s3::SelArgs) <= (size_t)r->B * tpe * 16 * sizeof(float)) {
-    selp = reinterpret_cast<s3::SelArgs *>(logits);
-    s3::SelArgs q{};
-    q.on = 1; q.mode = r->select_mode; q.uniform = r->uniform;
-    q.forced = r->forced_idx; q.forced_stride = r->T;
-    q.idx = r->idx; q.idx_stride = r->T; q.slot = r->slot; q.slot_stride = r->T; q.log_prob = r->log_prob; q.lp_stride = r->T;
-    q.zt = r->zt; q.zt_stride = zw; q.zt_width = zw; q.role_out = r->role; q.range_flag = c.flag();
-    hipLaunchKernelGGL(s3::sel_args_kernel, dim3((r->T + 63) / 64), dim3(64), 0, c.st, q, (int)r->T, (long)r->B, selp);
-    CHECK_LAUNCH();
-  }
   for (int t = 0; t < r->T; ++t) {
     c.g.n_ctx = r->n_ctx0 + t;
     s3::StepArgs sa{};

@@ -50,7 +50,11 @@ __host__ __device__ inline int layer_bytes(int F) { return round_kb(layer_pairs(
 __host__ __device__ inline int head_pairs(int F) { return F / 16; }
 __host__ __device__ inline int head_params(int F) { return 4 * F + 4; }
 __host__ __device__ inline int head_bytes(int F) { return round_kb(head_pairs(F) * PAIR_BYTES + head_params(F) * 4); }
-__host__ __device__ inline long image_words(int L, int F, int C) { return ((long)L * layer_bytes(F) + (long)(1 + C) * head_bytes(F)) / 4; }
+// embedder image (x-embedder, then y-embedder; behind the head images): W2 pairs [F/16] ((c, m): 2 c + m), then fp32 b2 [D] | b1 [F] | w1 [F][K]
+constexpr int emb_pairs(int F) { return F / 16; }
+constexpr int emb_bytes(int F) { return (emb_pairs(F) * PAIR_BYTES + (D + 9 * F) * 4 + 1023) & ~1023; }      // (K <= 8 input columns)
+__host__ __device__ inline long emb_offset_words(int L, int F, int C) { return ((long)L * layer_bytes(F) + (long)(1 + C) * head_bytes(F)) / 4; }
+__host__ __device__ inline long image_words(int L, int F, int C) { return emb_offset_words(L, F, C) + 2 * emb_bytes(F) / 4; }
 
 // activation image in 16-byte pieces: [tile][hi | lo][lane = 16 g + row % 16]; a piece holds features 4 g + (0..3) and
 // 16 + 4 g + (0..3) of its token row (= the B fragment element order of the single k-step)
@@ -79,6 +83,7 @@ struct PackArgs {
       *lin2_b[8], *n1w[8], *n1b[8], *n2w[8], *n2b[8];
   const float *acq_w1, *acq_b1, *acq_w2, *acq_b2;
   const float *gmm_w1[16], *gmm_b1[16], *gmm_w2[16], *gmm_b2[16];
+  const float *emb_w1[2], *emb_b1[2], *emb_w2[2], *emb_b2[2]; int emb_K[2];      // x-embedder, y-embedder (model/embedder.py:47-57)
   unsigned *out;
   unsigned *range_flag;
   int time_token;      // model.time_token: the acquisition head's W1 is [F, d + 1] (model/head.py:24-25); its last column goes to the
@@ -116,6 +121,18 @@ __global__ void pack_kernel(PackArgs a) {
         }
         v = __float_as_uint(f);
       }
+    } else if (i >= emb_offset_words(a.L, F, a.C)) {
+      const long oe = i - emb_offset_words(a.L, F, a.C), ew = emb_bytes(F) / 4, nfw = (long)emb_pairs(F) * PAIR_WORDS;
+      const int k = oe / ew, K = a.emb_K[k];          // 0: x-embedder, 1: y-embedder
+      const long o = oe % ew;
+      if (o < nfw) {                                  // pair (c, m) = k-step c of output tile m
+        const int p = o / PAIR_WORDS;
+        v = x3::pair_word(a.emb_w2[k], F, 16 * (p & 1), p >> 1, (int)(o % PAIR_WORDS), WSCALE, a.range_flag);
+      } else {
+        const int q = o - nfw;
+        const float f = q < D ? a.emb_b2[k][q] : q < D + F ? a.emb_b1[k][q - D] : q < D + F + F * K ? a.emb_w1[k][q - D - F] : 0.f;
+        v = __float_as_uint(f);
+      }
     } else {
       const long oh = i - a.L * lw;
       const int k = oh / hw;                          // 0: acquisition head, 1 + c: GMM head c
@@ -137,7 +154,8 @@ __global__ void pack_kernel(PackArgs a) {
   }
 }
 
-// ---- X0 image from the cached fp32 point embeddings (model/embedder.py:128-214) ----------------------------------
+// ---- rows of the X0 image from the cached fp32 point embeddings (model/embedder.py:128-214): the embedder kernel writes the image of
+// step 0 from its registers; the step kernel re-assembles the row of the point chosen at the previous step (Ex + Ey) ----------------
 struct AsmArgs {
   Geo g; int tpe;
   const float *Ex, *Ey; int ey_rows; const float *theta_tokens;
@@ -164,18 +182,6 @@ __device__ __forceinline__ void store_split8(u32x4 *X, long tile, int lane, cons
   X[xpiece(tile, 0, lane)] = __builtin_bit_cast(u32x4, h);
   X[xpiece(tile, 1, lane)] = __builtin_bit_cast(u32x4, l);
 }
-__global__ void assemble_kernel(AsmArgs a) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long tiles = (long)a.g.B * a.tpe;
-  if (i >= tiles * 64) return;
-  const int lane = i & 63, gq = lane >> 4;
-  const long tile = i >> 6;
-  const int b = tile / a.tpe, row = (int)(tile % a.tpe) * 16 + (lane & 15);
-  f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-  if (row < a.g.N) embed_row8(a, b, row, 4 * gq, lo, hi);
-  x3::range_check8(a.range_flag, lo, hi);
-  store_split8(a.X, tile, lane, lo, hi);
-}
 
 // ---- helpers of the step kernel ------------------------------------------------------------------------------------
 // `bytes` (whole KB) from global to LDS, 1 KB pieces round-robin over the waves
@@ -190,78 +196,125 @@ __device__ __forceinline__ Frag lds_pair(const char *base, int pair, int lane) {
 __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ float relu_s(float v) { return fmaxf(v, 0.f); }
 
-// ---- point embedders (model/embedder.py:47-57): E = W2 relu(W1 x + b1) + b2 for every point / target-data row ---------
-// One kernel instead of the generic pair (hidden layer kernel + GEMM): the F hidden units of a 16-row tile stay in
-// registers (first layer on the VALU: K = dim_x or dim_y <= 8 inputs), the second layer is the usual 3-term f16 split.
-// A workgroup packs the W2 fragment pairs it needs into LDS itself (16 KB at F = 128).
+// ---- point embedders (model/embedder.py:47-57): E = W2 relu(W1 x + b1) + b2 for every point / target-data row, and the X0 image --
+// The F hidden units of a 16-row tile stay in registers (first layer on the VALU: K = dim_x or dim_y <= 8 inputs), the second layer is
+// the usual 3-term f16 split.  A workgroup LDS-DMAs the two embedder images pack_kernel wrote (2 x 21 KB at F = 128) and its waves walk
+// tiles of 16 consecutive x rows (points, then target-data rows, of every episode): the x-embedding of the tile, the y-embedding of
+// the same rows where the tile holds point rows, Ex / Ey as fp32 rows (the step kernel patches chosen rows from them), and -- from the
+// same registers -- the rows' pieces of the X0 image: Ex, + Ey in fp32 on the rows that are context at step 0, then split
+// (embed_row8's order).  The next tile's inputs are requested before the current tile is computed.  The kernel's tail writes what
+// no embedder row covers: the theta-token rows and the zero rows behind row N of every episode's last tile.
 struct EmbArgs {
-  Src3 src; int rows_per_ep, B, K;
-  const float *w1, *b1, *w2, *b2;       // [F, K], [F], [D, F], [D]
-  float *E;                             // [B * rows_per_ep, D] fp32 rows
-  unsigned *range_flag;                 // f16 range guard: W2, and (through the assembled input image) the hidden units
+  const float *px, *tx, *py;            // point_x [B, P, Kx], target_x [B, n_td, Kx], point_y [B, P, Ky]
+  int B, P, n_td, Kx, Ky;
+  int n_ctx0, N, tpe;                   // rows [0, n_ctx0) of an episode are its context at step 0; N token rows in tpe tiles
+  const unsigned *img;                  // x-embedder image, y-embedder image (emb_bytes(F) each)
+  float *Ex, *Ey;                       // [B * (P + n_td), D], [B * P, D] fp32 rows
+  const float *theta_tokens;            // [N - P - n_td, D]
+  u32x4 *X0;
+  unsigned *range_flag;                 // f16 range guard: the layer-0 input is checked where it is split (W2: where it is packed)
 };
-// bid / nwg: this workgroup's index among the nwg that embed `a` (embed_kernel embeds two row sets -- x and y -- in one launch)
+// one tile through one embedder (LDS image `im`): the lane's eight features 4 g + (0..3), 16 + 4 g + (0..3) of row `tok`
 template <int F>
-__device__ __forceinline__ void embed_body(const EmbArgs &a, unsigned bid, unsigned nwg, unsigned *wimg, float *prm) {
-  constexpr int NH = F / 16, PAIRS = F / 16;
-  const int tid = threadIdx.x, lane = tid & 63, tok = lane & 15, g = lane >> 4, wave = tid >> 6;
-  for (int e = tid; e < PAIRS * PAIR_WORDS; e += 256) {      // pair (c, m) = k-step c of output tile m
-    const int p = e / PAIR_WORDS;
-    wimg[e] = x3::pair_word(a.w2, F, 16 * (p & 1), p >> 1, e % PAIR_WORDS, WSCALE, bid == 0 ? a.range_flag : nullptr);
-  }
-  for (int i = tid; i < D; i += 256) prm[i] = a.b2[i];
-  for (int i = tid; i < F; i += 256) prm[D + i] = a.b1[i];
-  for (int i = tid; i < F * a.K; i += 256) prm[D + F + i] = a.w1[i];
-  __syncthreads();
-  const float *b2 = prm, *b1 = prm + D, *w1 = prm + D + F;
-  const long total = (long)a.B * a.rows_per_ep, ntiles = (total + 15) / 16;
-  const int K = a.K;
+__device__ __forceinline__ void embed_tile(const char *im, const float (&xin)[8], int K, int lane, int g, f32x4 &e0, f32x4 &e1) {
+  constexpr int NH = F / 16;
+  const float *b2 = reinterpret_cast<const float *>(im + emb_pairs(F) * PAIR_BYTES), *b1 = b2 + D, *w1 = b1 + F;
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  for (long tile = (long)bid * 4 + wave; tile < ntiles; tile += (long)nwg * 4) {
-    const long row = 16 * tile + tok, rr = min(row, total - 1);
-    const int b = rr / a.rows_per_ep, p = rr % a.rows_per_ep;
-    const float *x;
-    if (p < a.src.n[0]) x = a.src.p[0] + ((long)b * a.src.n[0] + p) * K;
-    else if (p < a.src.n[0] + a.src.n[1]) x = a.src.p[1] + ((long)b * a.src.n[1] + (p - a.src.n[0])) * K;
-    else x = a.src.p[2] + ((long)b * a.src.n[2] + (p - a.src.n[0] - a.src.n[1])) * K;
-    float xin[8];
+  f32x4 hid[NH];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) xin[k] = k < K ? x[k] : 0.f;
-    f32x4 hid[NH];
+  for (int i = 0; i < NH; ++i) hid[i] = ld4(b1 + 16 * i + 4 * g);
+  // hid[u] = b1[u] + sum_k x[k] w1[u][k], k ascending per unit; one wave-uniform branch per input column
+  // (compile-time indices: a runtime-indexed xin[] would live in scratch memory)
 #pragma unroll
-    for (int i = 0; i < NH; ++i)
+  for (int k = 0; k < 8; ++k)
+    if (k < K) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int u = 16 * i + 4 * g + r;
-        float acc = b1[u];
+      for (int i = 0; i < NH; ++i)
 #pragma unroll
-        for (int k = 0; k < 8; ++k)      // (compile-time indices: a runtime-indexed xin[] would live in scratch memory)
-          if (k < K) acc = fmaf(xin[k], w1[u * K + k], acc);
-        hid[i][r] = relu_s(acc);
-      }
-    f32x4 y0 = z4, y1 = z4;
-#pragma unroll
-    for (int c = 0; c < NH / 2; ++c) {
-      f16x8 hh, hl;
-      split_frag(hid[2 * c], hid[2 * c + 1], hh, hl);
-      const Frag v0 = lds_pair(reinterpret_cast<const char *>(wimg), 2 * c, lane), v1 = lds_pair(reinterpret_cast<const char *>(wimg), 2 * c + 1, lane);
-      mfma3(y0, v0.hi, v0.lo, hh, hl);
-      mfma3(y1, v1.hi, v1.lo, hh, hl);
+        for (int r = 0; r < 4; ++r) hid[i][r] = fmaf(xin[k], w1[(16 * i + 4 * g + r) * K + k], hid[i][r]);
     }
-    if (row < total) {
-      float *e = a.E + row * D;
-      *reinterpret_cast<f32x4 *>(e + 4 * g) = y0 * WINV + ld4(b2 + 4 * g);
-      *reinterpret_cast<f32x4 *>(e + 16 + 4 * g) = y1 * WINV + ld4(b2 + 16 + 4 * g);
+  f32x4 y0 = z4, y1 = z4;
+#pragma unroll
+  for (int c = 0; c < NH / 2; ++c) {
+    f16x8 hh, hl;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { hid[2 * c][r] = relu_s(hid[2 * c][r]); hid[2 * c + 1][r] = relu_s(hid[2 * c + 1][r]); }
+    split_frag(hid[2 * c], hid[2 * c + 1], hh, hl);
+    const Frag v0 = lds_pair(im, 2 * c, lane), v1 = lds_pair(im, 2 * c + 1, lane);
+    mfma3(y0, v0.hi, v0.lo, hh, hl);
+    mfma3(y1, v1.hi, v1.lo, hh, hl);
+  }
+  e0 = y0 * WINV + ld4(b2 + 4 * g);
+  e1 = y1 * WINV + ld4(b2 + 16 + 4 * g);
+}
+constexpr int EMB_WAVES = 4;      // (one wave per SIMD)
+template <int F>
+__global__ __launch_bounds__(EMB_WAVES * 64) void embed_kernel(EmbArgs a) {
+  constexpr int EB = emb_bytes(F);
+  __shared__ __attribute__((aligned(16))) char img[2 * EB];
+  const int tid = threadIdx.x, lane = tid & 63, tok = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (int piece = wave; piece < (2 * EB >> 10); piece += EMB_WAVES) glds16(reinterpret_cast<const char *>(a.img) + piece * 1024 + lane * 16, img + piece * 1024);
+  const int rpe = a.P + a.n_td, Kx = a.Kx, Ky = a.Ky;
+  const long total = (long)a.B * rpe, ntiles = (total + 15) / 16, stride = (long)gridDim.x * EMB_WAVES;
+  auto load_in = [&](long tile, float (&x)[8], float (&y)[8], int &b, int &p) {      // episode, row and inputs of the lane's row of `tile` (clamped: always readable)
+    const long rr = min(16 * min(tile, ntiles - 1) + tok, total - 1);
+    b = rr / rpe; p = rr - (long)b * rpe;
+    const float *xs = p < a.P ? a.px + ((long)b * a.P + p) * Kx : a.tx + ((long)b * a.n_td + (p - a.P)) * Kx;
+    const float *ys = a.py + ((long)b * a.P + min(p, a.P - 1)) * Ky;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { x[k] = k < Kx ? xs[k] : 0.f; y[k] = k < Ky ? ys[k] : 0.f; }
+  };
+  long tile = (long)blockIdx.x * EMB_WAVES + wave;
+  float xn[8], yn[8];
+  int bn, pn;
+  load_in(tile, xn, yn, bn, pn);
+  wait_vmcnt<0>();
+  __syncthreads();
+  for (; tile < ntiles; tile += stride) {
+    float x[8], y[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { x[k] = xn[k]; y[k] = yn[k]; }
+    const int b = bn, p = pn;
+    load_in(tile + stride, xn, yn, bn, pn);
+    const long row = 16 * tile + tok;
+    const bool valid = row < total;
+    f32x4 e0, e1;
+    embed_tile<F>(img, x, Kx, lane, g, e0, e1);
+    if (valid) {
+      float *e = a.Ex + row * D;
+      *reinterpret_cast<f32x4 *>(e + 4 * g) = e0;
+      *reinterpret_cast<f32x4 *>(e + 16 + 4 * g) = e1;
+    }
+    __builtin_amdgcn_sched_barrier(0);      // (the two embedders one after the other: interleaved they need twice the registers)
+    const bool point = valid && p < a.P;
+    if (__ballot(point)) {            // (wave-uniform: a tile of target-data rows only has no y rows)
+      f32x4 q0, q1;
+      embed_tile<F>(img + EB, y, Ky, lane, g, q0, q1);
+      if (point) {
+        float *e = a.Ey + ((long)b * a.P + p) * D;
+        *reinterpret_cast<f32x4 *>(e + 4 * g) = q0;
+        *reinterpret_cast<f32x4 *>(e + 16 + 4 * g) = q1;
+        if (p < a.n_ctx0) { e0 += q0; e1 += q1; }
+      }
+    }
+    if (valid) {
+      x3::range_check8(a.range_flag, e0, e1);
+      store_split8(a.X0, (long)b * a.tpe + (p >> 4), 16 * g + (p & 15), e0, e1);
     }
   }
-}
-// the first nwg_a workgroups embed `a` (the x rows), the rest `b` (the y rows; nwg_a == gridDim.x: one row set only)
-template <int F>
-__global__ __launch_bounds__(256) void embed_kernel(EmbArgs a, EmbArgs b, unsigned nwg_a) {
-  __shared__ __attribute__((aligned(16))) unsigned wimg[(F / 16) * PAIR_WORDS];
-  __shared__ float prm[D + F + F * 8];                       // b2 | b1 | w1 [F][K]
-  if (blockIdx.x < nwg_a) embed_body<F>(a, blockIdx.x, nwg_a, wimg, prm);
-  else embed_body<F>(b, blockIdx.x - nwg_a, gridDim.x - nwg_a, wimg, prm);
+  const int nrest = 16 * a.tpe - rpe;
+  for (long i = (long)blockIdx.x * blockDim.x + tid; i < (long)a.B * nrest * 4; i += (long)gridDim.x * blockDim.x) {
+    const int gq = i & 3, r = rpe + (int)((i >> 2) % nrest);
+    const long b = (i >> 2) / nrest;
+    f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
+    if (r < a.N) {
+      const float *t = a.theta_tokens + (r - rpe) * D + 4 * gq;
+      lo = ld4(t); hi = ld4(t + 16);
+    }
+    x3::range_check8(a.range_flag, lo, hi);
+    store_split8(a.X0, b * a.tpe + (r >> 4), 16 * gq + (r & 15), lo, hi);
+  }
 }
 
 // (a, b) = LayerNorm over the 32 features of each token: 8 values per lane x 4 lane groups, fp32, two passes
@@ -421,18 +474,29 @@ struct StepArgs {
 #endif
 };
 
-// the T argument sets of a rollout's in-kernel selections: the per-step pointers are the rollout's [.., T] arrays advanced by the step
-__global__ void sel_args_kernel(SelArgs base, int T, long B, SelArgs *__restrict__ out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= T) return;
-  SelArgs q = base;
-  if (q.uniform) q.uniform += (size_t)t * B;
-  if (q.forced) q.forced += t;
-  if (q.idx) q.idx += t;
-  if (q.slot) q.slot += t;
-  if (q.log_prob) q.log_prob += t;
-  if (q.zt) q.zt += (size_t)t * B * q.zt_stride;
-  out[t] = q;
+// The set-up of a rollout that raises no range flag, in ONE launch (three launches of a few waves each cost their dispatch and drain):
+//   the f16 range status words cleared (a kernel, not a memset node: see Ctx::clear_flag) -- no block of this launch raises the flag,
+//   and every kernel that can (pack_kernel first) is a later launch on the stream;
+//   role[b, p] = p + 1 for the initial context points, 0 for the candidates;
+//   the T argument sets of the in-kernel selections (out != null): the per-step pointers are the rollout's [.., T] arrays advanced by the step.
+__global__ void setup_kernel(unsigned *flag_words, int *role, long B, int P, int n_ctx0, SelArgs base, int T, SelArgs *__restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 16) flag_words[i] = 0u;
+  if (role && i < B * P) {
+    const int p = i % P;
+    role[i] = p < n_ctx0 ? p + 1 : 0;
+  }
+  if (out && blockIdx.x == 0)
+    for (int t = threadIdx.x; t < T; t += blockDim.x) {
+      SelArgs q = base;
+      if (q.uniform) q.uniform += (size_t)t * B;
+      if (q.forced) q.forced += t;
+      if (q.idx) q.idx += t;
+      if (q.slot) q.slot += t;
+      if (q.log_prob) q.log_prob += t;
+      if (q.zt) q.zt += (size_t)t * B * q.zt_stride;
+      out[t] = q;
+    }
 }
 
 // one wave: the selection of episode b from its logits in LDS (acq_select_wave_kernel, kernels.h, with lg[] read from LDS)
@@ -879,10 +943,12 @@ __global__ __launch_bounds__(NW * 64) void step_kernel(StepArgs a) {
 
 // ---- the C GMM heads (model/head.py:152-186) over the dense-row image of all steps' target rows --------------------
 // raw_c[j] = w2_c[j] . relu(W1_c z + b1_c) + b2_c[j]; a wave keeps GT tiles in registers and walks the components,
-// whose images take turns in LDS; the raw outputs of the workgroup's 512 rows collect in LDS and one thread per row
-// turns them into the mixture parameters (mean, softplus std + std_min, softmax weight: head.py:264-265 with
-// dim_y == 1) and the log-likelihood of the row's target value (utils/eval.py:200-207).
-constexpr int GT = 4, GROWS = WAVES * GT * 16;
+// whose images alternate between two LDS buffers: component c + 1's LDS-DMA is issued before component c's products, so its
+// round trip runs under them, and ONE barrier per component says both "image c has landed" and "image c - 1 is free".  The raw
+// outputs of the workgroup's GT * 128 rows collect in LDS and one thread per row turns them into the mixture parameters
+// (mean, softplus std + std_min, softmax weight: head.py:264-265 with dim_y == 1) and the log-likelihood of the row's target
+// value (utils/eval.py:200-207).  GT is the host's choice (gmm_tiles_per_wave): 2, or 1 when the tiles are too few to cover the CUs.
+__host__ __device__ inline int gmm_lds_bytes(int F, int C, int gt) { return 2 * head_bytes(F) + 3 * C * (WAVES * gt * 16) * 4; }
 struct GmmArgs {
   const u32x4 *Z; long ntiles, M;
   const unsigned *img; int C; float std_min;      // img: the first GMM head image
@@ -891,14 +957,15 @@ struct GmmArgs {
   float *ll;                                      // [M] or null
   unsigned *range_flag;                           // f16 range guard: raised when a log-likelihood is not finite
 };
-template <int F>
+template <int F, int GT>
 __global__ __launch_bounds__(THREADS) void gmm_kernel(GmmArgs a) {
+  constexpr int GROWS = WAVES * GT * 16;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, tok = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NH = F / 16;
   const int hb = head_bytes(F);
-  float *raw = reinterpret_cast<float *>(lds + hb);          // [3 C][GROWS]
+  float *raw = reinterpret_cast<float *>(lds + 2 * hb);      // [3 C][GROWS]
   const long tile0 = ((long)blockIdx.x * WAVES + wave) * GT;
   f16x8 zh[GT], zl[GT];
 #pragma unroll
@@ -907,19 +974,20 @@ __global__ __launch_bounds__(THREADS) void gmm_kernel(GmmArgs a) {
     zh[i] = __builtin_bit_cast(f16x8, a.Z[xpiece(tl, 0, lane)]);
     zl[i] = __builtin_bit_cast(f16x8, a.Z[xpiece(tl, 1, lane)]);
   }
-  const float *hp = reinterpret_cast<const float *>(lds + head_pairs(F) * PAIR_BYTES);   // b1 | w2 [3] | b2
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  dma_copy(reinterpret_cast<const char *>(a.img), lds, hb, wave, lane);
   for (int c = 0; c < a.C; ++c) {
-    __syncthreads();
-    dma_copy(reinterpret_cast<const char *>(a.img) + (long)c * hb, lds, hb, wave, lane);
-    wait_vmcnt<0>();
-    __syncthreads();
+    const char *wh = lds + (c & 1) * hb;
+    const float *hp = reinterpret_cast<const float *>(wh + head_pairs(F) * PAIR_BYTES);   // b1 | w2 [3] | b2
+    wait_vmcnt<0>();      // this wave's pieces of image c (in flight since the barrier of component c - 1)
+    __syncthreads();      // every wave's pieces have landed, and every wave is through with image c - 1
+    if (c + 1 < a.C) dma_copy(reinterpret_cast<const char *>(a.img) + (long)(c + 1) * hb, lds + ((c + 1) & 1) * hb, hb, wave, lane);
 #pragma unroll
     for (int i = 0; i < GT; ++i) {
       f32x4 hid[NH];
 #pragma unroll
       for (int t = 0; t < NH; ++t) {
-        const Frag u = lds_pair(lds, t, lane);
+        const Frag u = lds_pair(wh, t, lane);
         hid[t] = z4;
         mfma3(hid[t], u.hi, u.lo, zh[i], zl[i]);
       }
@@ -943,7 +1011,7 @@ __global__ __launch_bounds__(THREADS) void gmm_kernel(GmmArgs a) {
   }
   __syncthreads();
   const long row = (long)blockIdx.x * GROWS + tid;
-  if (row >= a.M) return;
+  if (tid >= GROWS || row >= a.M) return;
   const float *rr = raw + tid;
   float mxw = -INFINITY;
   for (int c = 0; c < a.C; ++c) mxw = fmaxf(mxw, rr[(3 * c + 2) * GROWS]);

@@ -315,7 +315,6 @@ enum { ALINE_DBG_DISABLE_FUSED = 1u << 0,      /* fused::rollout_f32_kernel off 
        ALINE_DBG_NO_LAYER_TAIL = 1u << 5,      /* generic d = 32 pipeline on per-op kernels */
        ALINE_DBG_FULL_QKV = 1u << 6,           /* generic pipeline: K / V of every row (as the reference) */
        ALINE_DBG_VALU_ATTENTION = 1u << 7,     /* generic pipeline: fp32 VALU attention instead of attn3 */
-       ALINE_DBG_S3_GENERIC_EMBED = 1u << 8,   /* s3: point embedders on the generic kernels */
        ALINE_DBG_CES_GENERIC = 1u << 9,        /* CES likelihood: powf formulation */
        ALINE_DBG_FUSED_STAMPS = 1u << 10,      /* in-kernel phase stamps (diagnostic instantiations) */
        ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE = 1u << 11,  /* per-op backward at d = 256 / 512: forward recompute on the generic kernels instead of x3 / x5 layer_save_kernel */
@@ -335,8 +334,9 @@ enum { ALINE_DBG_DISABLE_FUSED = 1u << 0,      /* fused::rollout_f32_kernel off 
        ALINE_DBG_BWD_GRAD_F32 = 1u << 30 };     /* per-op backward of an F16X3 model: gradient products (dX, dW) in exact fp32 instead of the scaled f16 split */
 uint32_t aline_debug_set_flags(uint32_t flags);
 uint32_t aline_debug_get_flags(void);
-/* Integer knobs of the same kind (0 = automatic): launch shape of the s3 step kernel, precision of the backward GEMMs. */
-enum { ALINE_DBG_S3_WAVES = 0, ALINE_DBG_S3_EPW = 1, ALINE_DBG_BWD_PREC = 2, ALINE_DBG_NPARAMS = 3 };
+/* Integer knobs of the same kind (0 = automatic): launch shape of the s3 step kernel, precision of the backward GEMMs,
+   tiles per wave of the s3 GMM kernel (1 or 2). */
+enum { ALINE_DBG_S3_WAVES = 0, ALINE_DBG_S3_EPW = 1, ALINE_DBG_BWD_PREC = 2, ALINE_DBG_S3_GMM_GT = 3, ALINE_DBG_NPARAMS = 4 };
 int aline_debug_set_param(int key, int value);
 int aline_debug_get_param(int key);      /* the knob's current value (0 for an unknown key) */
 /* Byte offset, inside a rollout workspace, of the per-phase cycle stamps the fused rollout kernel
