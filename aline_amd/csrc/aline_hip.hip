@@ -52,12 +52,15 @@ constexpr size_t kGmmChunkRows = 32768;   // rows per post-loop GMM chunk (hidde
 
 // Workspace plan (offsets in floats).  One plan serves the step API and the rollout API.
 struct Plan {
+  int xGroups;     // x3 path: blocks of 64 keys in an episode's key list / key image / K-V buffer (x3_impl.h, KV_EP); 1 = the 64-key layout
   size_t Flag, xKX, xKpos, Ex, Ey, Hid, X, X1, QKV, A, Tm, Wacq, scalar, Wpack, Stamps, Ztg, xImg, xIn, xA, xB, xKV, xKeys, xKcnt, xLog, xZimg, xRaw, xRawQ, sImg, sX0, sXW, sLog, sZimg, sZq, sRaw, KeyIdx, Kcnt, X0, total;
   int qgmm_chunk;  // episodes per query-GMM chunk
 };
 
-Plan make_plan(const aline_model &m, int B, int P, int n_td, int ey_rows, bool query_gmm, int T = 0) {
+// max_keys: the most keys an episode shows at a step of the rollout (0: not a rollout) -- sizes the x3 path's key buffers
+Plan make_plan(const aline_model &m, int B, int P, int n_td, int ey_rows, bool query_gmm, int T = 0, int max_keys = 0) {
   Plan p{};
+  p.xGroups = 1;
   const size_t N = (size_t)P + n_td + m.n_theta, M = (size_t)B * N, d = m.d, F = m.F;
   const size_t n_t = (size_t)n_td + m.n_theta;
   const size_t Cc = (size_t)std::max(m.C, 1);
@@ -97,9 +100,10 @@ Plan make_plan(const aline_model &m, int B, int P, int n_td, int ey_rows, bool q
     const size_t tpe = (N + 15) / 16, img = pieces((long)B * tpe);
     p.xImg = take((size_t)(w5 ? x5::image_words(m.L, m.F, m.C) : x3::image_words(m.L, m.F, m.C)));
     p.xIn = take(img); p.xA = take(img); p.xB = take(img);
-    p.xKV = take((size_t)B * (w5 ? x5::KV_EP : x3::KV_EP) * 4);
-    p.xKeys = take((size_t)B * x3::WNK); p.xKcnt = take((size_t)B * 2);
-    p.xKX = take(pieces((long)B * (x3::WNK / 16)));                           // key image (key rows of the layer input, key-list order)
+    const size_t kg = p.xGroups = w5 ? 1 : x3::key_groups(max_keys);
+    p.xKV = take((size_t)B * kg * (w5 ? x5::KV_EP : x3::KV_EP) * 4);
+    p.xKeys = take((size_t)B * kg * x3::WNK); p.xKcnt = take((size_t)B * 2);
+    p.xKX = take(pieces((long)B * kg * (x3::WNK / 16)));                           // key image (key rows of the layer input, key-list order)
     p.xKpos = take((size_t)B * tpe * 16 / 2 + 1);                             // short [B][16 tpe]
     p.xLog = take((size_t)B * tpe * 16);
     p.xZimg = take(pieces(((long)T * B * n_t + 15) / 16));
@@ -117,6 +121,10 @@ Plan make_plan(const aline_model &m, int B, int P, int n_td, int ey_rows, bool q
   }
   p.total = off;
   return p;
+}
+
+static Plan rollout_plan(const aline_model &m, const aline_rollout &r, bool query_gmm) {
+  return make_plan(m, r.B, r.P, r.n_target_data, r.P, query_gmm, r.T, r.n_ctx0 + r.T - 1 + r.n_target_data + m.n_theta);
 }
 
 enum { ST_EMBED = 1, ST_ENC = 2, ST_HEAD = 4, ST_ALL = 7 };
@@ -771,7 +779,7 @@ static int rollout_ctx(const aline_model *m, const aline_rollout *r, void *ws, s
   c.g.tmask = r->target_mask;
   c.g.inst_B = 0; c.g.inst_t0 = 0; c.g.n_ctx0 = r->n_ctx0;
   c.m = m;
-  c.pl = make_plan(*m, r->B, r->P, r->n_target_data, r->P, wants_postq(*r), r->T);
+  c.pl = rollout_plan(*m, *r, wants_postq(*r));
   if (ws_bytes < c.pl.total * sizeof(float)) return ALINE_EWORKSPACE;
   c.ws = static_cast<float *>(ws);
   c.st = static_cast<hipStream_t>(stream);
@@ -780,7 +788,7 @@ static int rollout_ctx(const aline_model *m, const aline_rollout *r, void *ws, s
 
 size_t aline_rollout_workspace_bytes(const aline_model *m, const aline_rollout *r) {
   if (!m || !r || validate_model(*m, 0) != 0) return 0;
-  return make_plan(*m, r->B, r->P, r->n_target_data, r->P, wants_postq(*r), r->T).total * sizeof(float);
+  return rollout_plan(*m, *r, wants_postq(*r)).total * sizeof(float);
 }
 
 int aline_rollout_init(const aline_model *m, const aline_rollout *r, void *ws, size_t ws_bytes,
@@ -936,11 +944,15 @@ static int rollout_fused(const aline_model *m, const aline_rollout *r, void *ws,
 
 extern "C++" {
 #define X3_NS x3
+#define X3_LONGKEYS 1
 #include "x3_host.h"
 #undef X3_NS
+#undef X3_LONGKEYS
 #define X3_NS x5
+#define X3_LONGKEYS 0
 #include "x3_host.h"
 #undef X3_NS
+#undef X3_LONGKEYS
 }
 
 // The s3 path (s3.h): d = 32 / 4 heads at reference precision, any embedding mode, up to 160 keys per episode -- one
@@ -1092,7 +1104,7 @@ int aline_rollout_kernel_name(const aline_model *m, const aline_rollout *r, char
   if (path < 0) return path;
   switch (path) {
     case ALINE_PATH_FUSED: snprintf(buf, n, "fused::rollout_f32_kernel<%s>", dbg(ALINE_DBG_FUSED_STAMPS) ? "true" : "false"); break;
-    case ALINE_PATH_X3: snprintf(buf, n, "x3::layer_kernel<true>"); break;      // (the launch the event pair brackets: last layer of the last step)
+    case ALINE_PATH_X3: snprintf(buf, n, x3::long_keys(*m, *r) ? "x3::layer_long_kernel<true>" : "x3::layer_kernel<true>"); break;      // (the launch the event pair brackets: last layer of the last step)
     case ALINE_PATH_X5: snprintf(buf, n, "x5::layer_kernel<true>"); break;
     case ALINE_PATH_S3: {
       const S3Shape sh = s3_shape(*m, *r);
@@ -1257,14 +1269,14 @@ int aline_eig_ces_history(const float *theta, const float *xi, const float *y, i
 // Diagnostic only: byte offset of the stamp block inside a rollout workspace (tools/stamps.py).
 extern "C" size_t aline_debug_stamps_offset(const aline_model *m, const aline_rollout *r) {
   if (!m || !r) return 0;
-  return make_plan(*m, r->B, r->P, r->n_target_data, r->P, false, r->T).Stamps * sizeof(float);
+  return rollout_plan(*m, *r, false).Stamps * sizeof(float);
 }
 
 // Diagnostic only: byte offsets of the buffers the stamped diagnostic builds (X3_STAMPS / S3_STAMPS, tools/*_stamps.py) and
 // read back; declared in include/aline_hip.h.
 extern "C" size_t aline_debug_xraw_offset(const aline_model *m, const aline_rollout *r) {
   if (!m || !r) return 0;
-  const Plan pl = make_plan(*m, r->B, r->P, r->n_target_data, r->P, false, r->T);
+  const Plan pl = rollout_plan(*m, *r, false);
   return (m->d == s3::D ? pl.sRaw : pl.xRaw) * sizeof(float);
 }
 

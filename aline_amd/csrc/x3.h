@@ -7,11 +7,20 @@
 #pragma once
 #include "tile_image.h"
 
+// Kernels added since round 4 are compiled without the packed fp32 instructions (v_pk_add / mul / fma_f32): a per-kernel target
+// attribute, so that the kernels from before keep the code they have.  (Device pass only: the host compiler does not know the feature.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define X3_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define X3_NO_PK_F32
+#endif
+
 #define X3_NS x3
 #define X3_D 256
 #define X3_HD 32
 #define X3_THREADS 512
 #define X3_KV_AHEAD 1
+#define X3_LONGKEYS 1      // rollouts with 65 .. 160 visible keys: the long-key variants (x3_impl.h, KV_EP)
 #ifndef X3_ILV256
 #define X3_ILV256 1
 #endif
@@ -22,12 +31,14 @@
 #undef X3_HD
 #undef X3_THREADS
 #undef X3_KV_AHEAD
+#undef X3_LONGKEYS
 #undef X3_INTERLEAVE
 
 #define X3_NS x5
 #define X3_D 512
 #define X3_HD 64
 #define X3_THREADS 256
+#define X3_LONGKEYS 0      // (one wave per SIMD with its register file full: 64 keys at most)
 #ifndef X5_KV_AHEAD
 #define X5_KV_AHEAD 1
 #endif
@@ -42,4 +53,5 @@
 #undef X3_HD
 #undef X3_THREADS
 #undef X3_KV_AHEAD
+#undef X3_LONGKEYS
 #undef X3_INTERLEAVE

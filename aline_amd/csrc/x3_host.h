@@ -101,14 +101,17 @@ static int recompute(const aline_model *m, const Geo &g, int max_keys, const flo
 }
 
 // Eligibility of the tile-image path of this width (x3: d = 256 / 8 heads of 32, x5: d = 512 / 8 heads of 64) at reference
-// precision -- every product a 3-term f16 split on the matrix pipe.
+// precision -- every product a 3-term f16 split on the matrix pipe.  Up to NK_MAX visible keys per episode: 64, or 160 where the
+// width has the long-key variants (x3), which a rollout takes as a whole iff some step of it shows more than 64 (long_keys()).
+static int max_keys(const aline_model &m, const aline_rollout &r) { return r.n_ctx0 + r.T - 1 + r.n_target_data + m.n_theta; }
 static bool eligible(const aline_model &m, const aline_rollout &r) {
   if (dbg(ALINE_DBG_DISABLE_X3)) return false;
   if (m.precision != ALINE_PREC_F16X3 || m.d != D || m.H != H || m.F % 32) return false;
-  if (r.n_ctx0 + r.T - 1 + r.n_target_data + m.n_theta > WNK) return false;
+  if (max_keys(m, r) > NK_MAX) return false;
   if ((size_t)NBUF * CHUNK_BYTES + (size_t)std::max(layer_params(m.F), head_lds_params(m.F)) * 4 > 160 * 1024) return false;
   return true;
 }
+static bool long_keys(const aline_model &m, const aline_rollout &r) { return key_groups(max_keys(m, r)) > 1; }
 
 static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_t ws_bytes, void *stream) {
   Ctx c;
@@ -146,12 +149,29 @@ static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
   const int cus = device_cus();
+  // the layout of the episode's keys (x3_impl.h, KV_EP): c.pl sized the key list, the key image and the K / V buffer for these groups
+  const int ktiles = 4 * c.pl.xGroups;
+#if X3_LONGKEYS
+  const bool lk = ktiles > WNK / 16;
+  if (lk) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_long_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_layer);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_long_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_layer);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_all_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_split_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+  }
+#else
+  if (ktiles != WNK / 16) return ALINE_EINVAL;
+#endif
   for (int t = 0; t < r->T; ++t) {
     c.g.n_ctx = r->n_ctx0 + t;
+#if X3_LONGKEYS
+    if (lk) hipLaunchKernelGGL(keys_long_kernel, dim3(r->B), dim3(256), 0, c.st, c.g, tpe, keyrow, kcnt, keypos, XIN, KX, ktiles);
+    else
+#endif
     hipLaunchKernelGGL(keys_kernel, dim3(r->B), dim3(256), 0, c.st, c.g, tpe, keyrow, kcnt, keypos, XIN, KX);
     CHECK_LAUNCH();
     const int nkeys = r->n_ctx0 + t + n_t;                      // upper bound of an episode's key count at this step
-    const int nkt2 = 2 * ((std::min(nkeys, WNK) + 31) / 32);
+    const int nkt2 = 2 * ((std::min(nkeys, 16 * ktiles) + 31) / 32);      // (every key tile an attention variant can read at this step is written at it)
     const u32x4 *xin = XIN;
     for (int l = 0; l < m->L; ++l) {
       u32x4 *xout = (l & 1) ? XB : XA;
@@ -160,10 +180,15 @@ static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_
       ka.ngroups = (int)(((long)r->B * nkt2 + WAVES - 1) / WAVES);
       // (groups of key tiles that do not fill the chip: one job -- K | V x channel half -- per workgroup, so that every CU streams)
       constexpr int NJ = 2 * CPK;
-      if ((ka.ngroups * NJ + cus - 1) / cus < NJ * ((ka.ngroups + cus - 1) / cus))      // fewer chunk passes per CU when split
-        hipLaunchKernelGGL(kv_split_kernel, dim3((unsigned)(std::min(ka.ngroups, std::max(1, cus / NJ)) * NJ)), dim3(THREADS), smem_kv, c.st, ka);
+      const bool split = (ka.ngroups * NJ + cus - 1) / cus < NJ * ((ka.ngroups + cus - 1) / cus);      // fewer chunk passes per CU when split
+      const dim3 kv_grid(split ? (unsigned)(std::min(ka.ngroups, std::max(1, cus / NJ)) * NJ) : (unsigned)std::min(ka.ngroups, cus));
+#if X3_LONGKEYS
+      if (lk && split) hipLaunchKernelGGL(kv_split_long_kernel, kv_grid, dim3(THREADS), smem_kv, c.st, ka, ktiles);
+      else if (lk) hipLaunchKernelGGL(kv_all_long_kernel, kv_grid, dim3(THREADS), smem_kv, c.st, ka, ktiles);
       else
-        hipLaunchKernelGGL(kv_all_kernel, dim3((unsigned)std::min(ka.ngroups, cus)), dim3(THREADS), smem_kv, c.st, ka);
+#endif
+      if (split) hipLaunchKernelGGL(kv_split_kernel, kv_grid, dim3(THREADS), smem_kv, c.st, ka);
+      else hipLaunchKernelGGL(kv_all_kernel, kv_grid, dim3(THREADS), smem_kv, c.st, ka);
       CHECK_LAUNCH();
       LayerArgs la{};
       la.g = c.g; la.tpe = tpe; la.ngroups = (int)((tiles + WAVES - 1) / WAVES);
@@ -175,8 +200,14 @@ static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_
 #endif
       const bool timed = (t == (r->ev_kernel_step > 0 ? r->ev_kernel_step - 1 : r->T - 1) && last);      // bench.py times this launch of the dominant kernel
       if (timed && r->ev_kernel_start) (void)hipEventRecord(static_cast<hipEvent_t>(r->ev_kernel_start), c.st);
-      if (last) hipLaunchKernelGGL(layer_kernel<true>, dim3((unsigned)std::min(la.ngroups, cus)), dim3(THREADS), smem_layer, c.st, la);
-      else hipLaunchKernelGGL(layer_kernel<false>, dim3((unsigned)std::min(la.ngroups, cus)), dim3(THREADS), smem_layer, c.st, la);
+      const dim3 layer_grid((unsigned)std::min(la.ngroups, cus));
+#if X3_LONGKEYS
+      if (lk && last) hipLaunchKernelGGL(layer_long_kernel<true>, layer_grid, dim3(THREADS), smem_layer, c.st, la, ktiles);
+      else if (lk) hipLaunchKernelGGL(layer_long_kernel<false>, layer_grid, dim3(THREADS), smem_layer, c.st, la, ktiles);
+      else
+#endif
+      if (last) hipLaunchKernelGGL(layer_kernel<true>, layer_grid, dim3(THREADS), smem_layer, c.st, la);
+      else hipLaunchKernelGGL(layer_kernel<false>, layer_grid, dim3(THREADS), smem_layer, c.st, la);
       if (timed && r->ev_kernel_stop) (void)hipEventRecord(static_cast<hipEvent_t>(r->ev_kernel_stop), c.st);
       CHECK_LAUNCH();
       xin = xout;

@@ -45,6 +45,11 @@ constexpr int PIECES_PER_WAVE = CHUNK_BYTES / 1024 / WAVES;
 constexpr float WSCALE = 256.f, WINV = 1.f / 256.f;
 constexpr long KV_VOFF = NKS * 512;                   // u32x4 per episode: K pairs [channel k-step NKS][kt 4] | V^T pairs [i NMT][s 2]
 constexpr long KV_EP = KV_VOFF + NMT * 256;
+// Long-key layout (X3_LONGKEYS widths: d = 256): a rollout that shows an episode more than WNK keys at some step runs on `groups` =
+// ceil(max keys / WNK) blocks of the KV_EP layout per episode -- key tile kt in block kt >> 2 at index kt & 3, V^T k-step s in block
+// s >> 1 at index s & 1 --, a key image of [B][4 groups] tiles and a key list of [B][64 groups] rows.  One group: today's layout.
+constexpr int NK_MAX = X3_LONGKEYS ? 160 : WNK;       // most keys of an episode the path serves (10 key tiles: s3::NK_MAX)
+__host__ __device__ inline int key_groups(int max_keys) { return (max_keys > WNK && max_keys <= NK_MAX) ? (max_keys + WNK - 1) / WNK : 1; }
 
 #ifndef XMFMA
 #define XMFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0)
@@ -273,8 +278,11 @@ __global__ __launch_bounds__(64) void patch_row_kernel(AsmArgs a, int order) {
 // layer 0 itself: the key rows of the input image gathered into [B][WNK / 16 key tiles] tiles of the usual piece layout, so
 // that kv_kernel reads whole KBs instead of 64 scattered 16-byte pieces per key row (a row of the token image shares each
 // of its 64-byte lines with three other rows: 4x read amplification; the gather was most of kv_kernel's time in round 2).
-__global__ __launch_bounds__(256) void keys_kernel(Geo g, int tpe, int *__restrict__ keyrow, int *__restrict__ kcnt,
-                                                   short *__restrict__ keypos, const u32x4 *__restrict__ X0, u32x4 *__restrict__ KX) {
+// (LONG: the long-key layout, `ktiles` = 4 groups key tiles per episode; else ktiles == WNK / 16, a constant)
+template <bool LONG>
+__device__ __forceinline__ void keys_body(const Geo &g, int tpe, int *__restrict__ keyrow, int *__restrict__ kcnt,
+                                          short *__restrict__ keypos, const u32x4 *__restrict__ X0, u32x4 *__restrict__ KX, int ktiles_rt) {
+  const int ktiles = LONG ? ktiles_rt : WNK / 16, cap = 16 * ktiles;      // key tiles / key slots of an episode
   __shared__ int wave_cnt[4];
   __shared__ int s_base, s_n;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -290,22 +298,22 @@ __global__ __launch_bounds__(256) void keys_kernel(Geo g, int tpe, int *__restri
     int off = s_base;
     for (int w = 0; w < wave; ++w) off += wave_cnt[w];
     const int k = off + __popcll(bal & ((1ull << lane) - 1ull));
-    if (key && k < WNK) { keyrow[b * WNK + k] = row; keypos[(long)b * 16 * tpe + row] = (short)k; }
+    if (key && k < cap) { keyrow[b * cap + k] = row; keypos[(long)b * 16 * tpe + row] = (short)k; }
     __syncthreads();
     if (tid == 0) s_base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
     __syncthreads();
   }
   if (tid == 0) {
-    int n = min(s_base, WNK);
+    int n = min(s_base, cap);
     kcnt[2 * b] = n;
     const int n_t = g.n_td + g.n_th;
     for (int j = 0; j < n_t; ++j)
-      if ((!g.tmask || g.tmask[j]) && n < WNK) { keyrow[b * WNK + n] = g.P + j; keypos[(long)b * 16 * tpe + g.P + j] = (short)n; ++n; }
+      if ((!g.tmask || g.tmask[j]) && n < cap) { keyrow[b * cap + n] = g.P + j; keypos[(long)b * 16 * tpe + g.P + j] = (short)n; ++n; }
     kcnt[2 * b + 1] = n;
     s_n = n;
   }
   __syncthreads();
-  // layer 0's key image: key k -> tile b * (WNK / 16) + k / 16, row k % 16; PPR = 8 NKS pieces (ks, hi | lo, g) of 16 bytes per key row
+  // layer 0's key image: key k -> tile b * ktiles + k / 16, row k % 16; PPR = 8 NKS pieces (ks, hi | lo, g) of 16 bytes per key row
   constexpr int PPR = 8 * NKS;
   const int n = s_n;
   for (int i0 = tid; i0 < n * PPR; i0 += 256 * 8) {          // 8 pieces per thread in flight (the loads miss L2: one at a time took 28 us)
@@ -313,16 +321,26 @@ __global__ __launch_bounds__(256) void keys_kernel(Geo g, int tpe, int *__restri
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = min(i0 + 256 * u, n * PPR - 1), k = i / PPR, e = i % PPR, ks = e >> 3, hl = (e >> 2) & 1, gq = e & 3;
-      const int row = keyrow[b * WNK + k];
+      const int row = keyrow[b * cap + k];
       v[u] = X0[xpiece((long)b * tpe + (row >> 4), ks, hl, 16 * gq + (row & 15))];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = i0 + 256 * u, k = i / PPR, e = i % PPR, ks = e >> 3, hl = (e >> 2) & 1, gq = e & 3;
-      if (i < n * PPR) KX[xpiece((long)b * (WNK / 16) + (k >> 4), ks, hl, 16 * gq + (k & 15))] = v[u];
+      if (i < n * PPR) KX[xpiece((long)b * ktiles + (k >> 4), ks, hl, 16 * gq + (k & 15))] = v[u];
     }
   }
 }
+__global__ __launch_bounds__(256) void keys_kernel(Geo g, int tpe, int *__restrict__ keyrow, int *__restrict__ kcnt,
+                                                   short *__restrict__ keypos, const u32x4 *__restrict__ X0, u32x4 *__restrict__ KX) {
+  keys_body<false>(g, tpe, keyrow, kcnt, keypos, X0, KX, 0);
+}
+#if X3_LONGKEYS
+__global__ __launch_bounds__(256) X3_NO_PK_F32 void keys_long_kernel(Geo g, int tpe, int *__restrict__ keyrow, int *__restrict__ kcnt,
+                                                        short *__restrict__ keypos, const u32x4 *__restrict__ X0, u32x4 *__restrict__ KX, int ktiles) {
+  keys_body<true>(g, tpe, keyrow, kcnt, keypos, X0, KX, ktiles);
+}
+#endif
 
 // ---- the weight stream ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void glds16(const void *gsrc, void *ldst) {
@@ -632,153 +650,15 @@ struct KvArgs {
   u32x4 *KV;
 };
 
-// A workgroup computes K and V of its group of WAVES key tiles (all 2 PC chunks of Wk | Wv per group).
-__global__ __launch_bounds__(THREADS) void kv_all_kernel(KvArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  float *prm = reinterpret_cast<float *>(lds + NBUF * CHUNK_BYTES);      // bk | bv
-  const int tid = threadIdx.x, lane = tid & 63, tok = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const float *gprm = reinterpret_cast<const float *>(a.img + (long)layer_chunks(a.F) * CHUNK_WORDS);
-  for (int i = tid; i < 2 * D; i += THREADS) prm[i] = gprm[D + i];
-  const char *wbase = reinterpret_cast<const char *>(a.img) + (long)PC * CHUNK_BYTES;     // K chunks, then V chunks
-  auto st = make_stream([wbase](int s) { return wbase + (long)s * CHUNK_BYTES; }, lds, 2 * PC, tid);
-  st.start();
-  __syncthreads();
-  st.sync();
-  FragRing ring;
-  const long ntiles = (long)a.g.B * a.nkt2;
-  for (int grp = blockIdx.x; grp < a.ngroups; grp += gridDim.x) {
-    const long tile = (long)grp * WAVES + wave;
-    const bool valid = tile < ntiles;
-    const long tl = valid ? tile : ntiles - 1;
-    const int b = tl / a.nkt2, kt = tl % a.nkt2, key = 16 * kt + tok;
-    const bool live = key < a.kcnt[2 * b + 1];          // (slots behind the key count hold stale rows: zeroed, the attention masks them)
-    f16x8 xh[NKS], xl[NKS];
-    load_tile(a.X, (long)b * (WNK / 16) + kt, lane, xh, xl);
-    if (!live) {
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) { xh[ks] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0}; xl[ks] = xh[ks]; }
-    }
-    u32x4 *kv = a.KV + (long)b * KV_EP;
-    f32x4 y[NMT];
-    // K^T = Wk KX^T: rows = channels, columns = keys -> A fragments of S^T = K Q^T, pair (channel k-step h, kt) -- a head is KPH k-steps
-#pragma unroll
-    for (int m = 0; m < NMT; ++m) y[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    chunk_run<PC>(st, ring, [&](int cc, int p, const f16x8 &ah, const f16x8 &al) { mfma3(y[16 * (cc % CPK) + p], ah, al, xh[cc / CPK], xl[cc / CPK]); });
-#pragma unroll
-    for (int h = 0; h < NKS; ++h) {
-      const f32x4 b0 = *reinterpret_cast<const f32x4 *>(prm + 32 * h + 4 * g), b1 = *reinterpret_cast<const f32x4 *>(prm + 32 * h + 16 + 4 * g);
-      f16x8 fh, fl;
-      split_frag(y[2 * h] * WINV + b0, y[2 * h + 1] * WINV + b1, fh, fl);
-      if (valid) {
-        kv[((h * 4 + kt) * 2) * 64 + lane] = __builtin_bit_cast(u32x4, fh);
-        kv[((h * 4 + kt) * 2 + 1) * 64 + lane] = __builtin_bit_cast(u32x4, fl);
-      }
-    }
-    // V = KX Wv^T with the MFMA operands swapped (rows = keys, columns = channels): accumulator tile i holds
-    // V[key 16 kt + 4 g + r][channel 16 i + tok] -- half (kt & 1) of this lane's piece of the V^T pair (i, kt / 2)
-#pragma unroll
-    for (int m = 0; m < NMT; ++m) y[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    chunk_run<PC>(st, ring, [&](int cc, int p, const f16x8 &bh, const f16x8 &bl) { mfma3(y[16 * (cc % CPK) + p], xh[cc / CPK], xl[cc / CPK], bh, bl); });
-#pragma unroll
-    for (int i = 0; i < NMT; ++i) {
-      const float bv = prm[D + 16 * i + tok];
-      unsigned h0, l0, h1, l1;
-      split2(y[i][0] * WINV + bv, y[i][1] * WINV + bv, h0, l0);
-      split2(y[i][2] * WINV + bv, y[i][3] * WINV + bv, h1, l1);
-      if (valid) {
-        u32x2 *ph = reinterpret_cast<u32x2 *>(kv + KV_VOFF + ((i * 2 + (kt >> 1)) * 2) * 64 + lane) + (kt & 1);
-        u32x2 *pl = reinterpret_cast<u32x2 *>(kv + KV_VOFF + ((i * 2 + (kt >> 1)) * 2 + 1) * 64 + lane) + (kt & 1);
-        *ph = (u32x2){h0, h1};
-        *pl = (u32x2){l0, l1};
-      }
-    }
-  }
-  st.finish();
-}
-
-// The same split into jobs -- (K | V) x (CPK halves of the D output channels): 16 output tiles and NKS chunks each --, one job per
-// workgroup (blockIdx % (2 CPK)), for launches with fewer groups of key tiles than CUs: at d = 512 / B = 256 there are 128 groups, each
-// streaming 2 MB of weights through one CU's LDS-DMA (60 us per launch, 14 % of the cfg5 rollout); split four ways every CU streams.
-__global__ __launch_bounds__(THREADS) void kv_split_kernel(KvArgs a) {
-  constexpr bool SPLIT = true;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  float *prm = reinterpret_cast<float *>(lds + NBUF * CHUNK_BYTES);      // bk | bv
-  const int tid = threadIdx.x, lane = tid & 63, tok = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const float *gprm = reinterpret_cast<const float *>(a.img + (long)layer_chunks(a.F) * CHUNK_WORDS);
-  for (int i = tid; i < 2 * D; i += THREADS) prm[i] = gprm[D + i];
-  constexpr int NJ = 2 * CPK;
-  const int job0 = SPLIT ? (int)(blockIdx.x % NJ) : 0;
-  const int grp0 = SPLIT ? (int)(blockIdx.x / NJ) : (int)blockIdx.x, gstride = SPLIT ? (int)(gridDim.x / NJ) : (int)gridDim.x;
-  const char *wbase = reinterpret_cast<const char *>(a.img) + (long)PC * CHUNK_BYTES;     // K chunks, then V chunks
-  // stream position s -> job (SPLIT: job0; else s / NKS), k-step s % NKS -> chunk (K | V) PC + CPK k + half
-  auto st = make_stream([wbase, job0](int s) {
-    const int job = SPLIT ? job0 : s / NKS, k = s % NKS;
-    return wbase + (long)((job / CPK) * PC + CPK * k + job % CPK) * CHUNK_BYTES;
-  }, lds, (SPLIT ? 1 : NJ) * NKS, tid);
-  st.start();
-  __syncthreads();
-  st.sync();
-  FragRing ring;
-  const long ntiles = (long)a.g.B * a.nkt2;
-  for (int grp = grp0; grp < a.ngroups; grp += gstride) {
-    const long tile = (long)grp * WAVES + wave;
-    const bool valid = tile < ntiles;
-    const long tl = valid ? tile : ntiles - 1;
-    const int b = tl / a.nkt2, kt = tl % a.nkt2, key = 16 * kt + tok;
-    const bool live = key < a.kcnt[2 * b + 1];          // (slots behind the key count hold stale rows: zeroed, the attention masks them)
-    f16x8 xh[NKS], xl[NKS];
-    load_tile(a.X, (long)b * (WNK / 16) + kt, lane, xh, xl);
-    if (!live) {
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) { xh[ks] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0}; xl[ks] = xh[ks]; }
-    }
-    u32x4 *kv = a.KV + (long)b * KV_EP;
-#pragma unroll
-    for (int job = 0; job < NJ; ++job) {      // (unrolled: the job, and with it every register index and parameter offset, is a constant)
-      if (SPLIT && job != job0) continue;
-      const int half = job % CPK;
-      f32x4 y[16];
-#pragma unroll
-      for (int m = 0; m < 16; ++m) y[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (job < CPK) {
-        // K^T = Wk KX^T: rows = channels, columns = keys -> A fragments of S^T = K Q^T, pair (channel k-step f, kt) -- a head is KPH k-steps
-        chunk_run<NKS>(st, ring, [&](int cc, int p, const f16x8 &ah, const f16x8 &al) { mfma3(y[p], ah, al, xh[cc], xl[cc]); });
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int f = 8 * half + j;
-          const f32x4 b0 = *reinterpret_cast<const f32x4 *>(prm + 32 * f + 4 * g), b1 = *reinterpret_cast<const f32x4 *>(prm + 32 * f + 16 + 4 * g);
-          f16x8 fh, fl;
-          split_frag(y[2 * j] * WINV + b0, y[2 * j + 1] * WINV + b1, fh, fl);
-          if (valid) {
-            kv[((f * 4 + kt) * 2) * 64 + lane] = __builtin_bit_cast(u32x4, fh);
-            kv[((f * 4 + kt) * 2 + 1) * 64 + lane] = __builtin_bit_cast(u32x4, fl);
-          }
-        }
-      } else {
-        // V = KX Wv^T with the MFMA operands swapped (rows = keys, columns = channels): accumulator tile i holds
-        // V[key 16 kt + 4 g + r][channel 16 i + tok] -- half (kt & 1) of this lane's piece of the V^T pair (i, kt / 2)
-        chunk_run<NKS>(st, ring, [&](int cc, int p, const f16x8 &bh, const f16x8 &bl) { mfma3(y[p], xh[cc], xl[cc], bh, bl); });
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int i = 16 * half + j;
-          const float bv = prm[D + 16 * i + tok];
-          unsigned h0, l0, h1, l1;
-          split2(y[j][0] * WINV + bv, y[j][1] * WINV + bv, h0, l0);
-          split2(y[j][2] * WINV + bv, y[j][3] * WINV + bv, h1, l1);
-          if (valid) {
-            u32x2 *ph = reinterpret_cast<u32x2 *>(kv + KV_VOFF + ((i * 2 + (kt >> 1)) * 2) * 64 + lane) + (kt & 1);
-            u32x2 *pl = reinterpret_cast<u32x2 *>(kv + KV_VOFF + ((i * 2 + (kt >> 1)) * 2 + 1) * 64 + lane) + (kt & 1);
-            *ph = (u32x2){h0, h1};
-            *pl = (u32x2){l0, l1};
-          }
-        }
-      }
-    }
-  }
-  st.finish();
-}
+// kv_all_kernel / kv_split_kernel, and their variants on the long-key layout
+#define X3_KV_LONG 0
+#include "x3_kv.h"
+#undef X3_KV_LONG
+#if X3_LONGKEYS
+#define X3_KV_LONG 1
+#include "x3_kv.h"
+#undef X3_KV_LONG
+#endif
 
 // ---- one encoder layer of a token tile ----------------------------------------------------------------------------
 struct LayerArgs {
@@ -890,11 +770,123 @@ __device__ __forceinline__ void attention_tile(f16x8 (&qh)[NKS], f16x8 (&ql)[NKS
   }
 }
 
+#if X3_LONGKEYS
+// ---- the same attention against 5 .. 10 key tiles (NKT = 6, 8, 10: 65 .. 160 keys, the long-key layout) ---------------------------
+// One exact softmax per head with ALL of its scores in registers (s[NKT]: up to 40 per lane), in two streamed phases:
+//   scores  S^T = K Q^T, a GROUP of 4 key tiles (one block of the episode's K / V buffer) at a time, then max / exp2 / sum as above;
+//   output  O^T = V^T P, a group of 2 V^T k-steps (64 keys, the same block) at a time.
+// The K pairs and the V^T pairs of a head are never live together: a group of either is one UNIT of 8 KPH fragments (32 registers at
+// d = 256), and the units of the tile -- head by head, K groups then V groups -- go through a ring of two: unit u + 1 is requested from
+// L2 before unit u is computed (HeadKV's request-ahead, along (head, phase, group) instead of along heads).  64 registers of fragments
+// in flight instead of the 2 x 64 of attention_tile<4>, which is the room the scores need at two waves per SIMD.  Arithmetic and
+// summation order are those of attention_tile: no running maximum, no rescaling.  The visibility mask is recomputed from nv per
+// head (a compare + select per score) instead of being kept (40 more registers).
+constexpr int LK_UNIT = 8 * KPH;
+template <int NKT>
+__device__ __forceinline__ void long_unit_load(u32x4 (&d)[LK_UNIT], const u32x4 *kv, int u) {
+  constexpr int G = (NKT + 3) / 4;
+  const int h = u / (2 * G), w = u % (2 * G);           // (u is a constant of the unrolled loops)
+  if (w < G) {                                          // K pairs of key tiles 4 w + t of head h
+    const u32x4 *p = kv + (long)w * KV_EP;
+#pragma unroll
+    for (int j = 0; j < KPH; ++j)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (4 * w + t < NKT) {
+          d[2 * (j * 4 + t)] = p[(((h * KPH + j) * 4 + t) * 2) * 64];
+          d[2 * (j * 4 + t) + 1] = p[(((h * KPH + j) * 4 + t) * 2 + 1) * 64];
+        }
+  } else {                                              // V^T pairs of k-steps 2 (w - G) + si, channel tiles MPH h + ii
+    const u32x4 *p = kv + (long)(w - G) * KV_EP + KV_VOFF;
+#pragma unroll
+    for (int ii = 0; ii < MPH; ++ii)
+#pragma unroll
+      for (int si = 0; si < 2; ++si)
+        if (4 * (w - G) + 2 * si < NKT) {
+          const u32x4 *vp = p + (((MPH * h + ii) * 2 + si) * 2) * 64;
+          d[(ii * 2 + si) * 2] = vp[0]; d[(ii * 2 + si) * 2 + 1] = vp[64];
+        }
+  }
+}
+// NKT even (the K / V kernels write whole V^T k-steps: key tiles in pairs); `first` = unit 0, requested by the caller
+template <int NKT>
+__device__ __forceinline__ void attention_long(f16x8 (&qh)[NKS], f16x8 (&ql)[NKS], const u32x4 *kv, int nv, const u32x4 (&first)[LK_UNIT]) {
+  static_assert(NKT % 2 == 0 && NKT > 4 && 16 * NKT <= NK_MAX && MPH == 2 * KPH, "long-key attention: 6, 8 or 10 key tiles");
+  constexpr int G = (NKT + 3) / 4, UPH = 2 * G, NU = H * UPH;
+  const float inf = opaque_inf();
+  u32x4 buf[2][LK_UNIT];
+#pragma unroll
+  for (int i = 0; i < LK_UNIT; ++i) buf[0][i] = first[i];
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    int nvh = nv;
+    asm volatile("" : "+v"(nvh));                       // (opaque: the 4 NKT mask values are recomputed, not carried from head to head)
+    f32x4 s[NKT];
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) {
+      const int u = h * UPH + gi;
+      if (u + 1 < NU) long_unit_load<NKT>(buf[(u + 1) & 1], kv, u + 1);
+      __builtin_amdgcn_sched_barrier(0);                // (the request stays in front of the unit it hides behind)
+      const u32x4 (&c)[LK_UNIT] = buf[u & 1];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int kt = 4 * gi + t;
+        if (kt < NKT) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s[kt][r] = (16 * kt + r) < nvh ? 0.f : -INFINITY;
+#pragma unroll
+          for (int j = 0; j < KPH; ++j)
+            mfma3(s[kt], __builtin_bit_cast(f16x8, c[2 * (j * 4 + t)]), __builtin_bit_cast(f16x8, c[2 * (j * 4 + t) + 1]), qh[h * KPH + j], ql[h * KPH + j]);
+        }
+      }
+    }
+    float mx = vmax(vmax(s[0][0], s[0][1], inf), vmax(s[0][2], s[0][3], inf), inf);
+#pragma unroll
+    for (int kt = 1; kt < NKT; ++kt) mx = vmax(mx, vmax(vmax(s[kt][0], s[kt][1], inf), vmax(s[kt][2], s[kt][3], inf), inf), inf);
+    mx = group_max4(mx, inf);
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s[kt][r] = __builtin_amdgcn_exp2f(s[kt][r] - mx);
+        sum += s[kt][r];
+      }
+    const float inv = __builtin_amdgcn_rcpf(group_sum4(sum));
+    f32x4 o[MPH];
+#pragma unroll
+    for (int ii = 0; ii < MPH; ++ii) o[ii] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) {
+      const int u = h * UPH + G + gi;
+      if (u + 1 < NU) long_unit_load<NKT>(buf[(u + 1) & 1], kv, u + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      const u32x4 (&c)[LK_UNIT] = buf[u & 1];
+#pragma unroll
+      for (int si = 0; si < 2; ++si) {
+        const int ks = 2 * gi + si;                     // V^T k-step: key tiles 2 ks, 2 ks + 1
+        if (2 * ks < NKT) {
+          f16x8 ph, pl;
+          split_frag(s[2 * ks], s[2 * ks + 1], ph, pl);
+#pragma unroll
+          for (int ii = 0; ii < MPH; ++ii)
+            mfma3(o[ii], __builtin_bit_cast(f16x8, c[(ii * 2 + si) * 2]), __builtin_bit_cast(f16x8, c[(ii * 2 + si) * 2 + 1]), ph, pl);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < KPH; ++j) split_frag(o[2 * j] * inv, o[2 * j + 1] * inv, qh[h * KPH + j], ql[h * KPH + j]);
+  }
+}
+#endif
+
 // fp32 side outputs of layer_save_kernel: written once, read by other kernels much later -- streaming stores
 __device__ __forceinline__ void sv_store(float *p, const f32x4 &v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(p)); }
 
-template <bool LAST, bool SAVE>
-__device__ __forceinline__ void layer_body(const LayerArgs &a) {
+// (LONG: the long-key layout of `ktiles` = 4 groups key tiles per episode -- see KV_EP -- and attention against up to 10 key tiles)
+template <bool LAST, bool SAVE, bool LONG = false>
+__device__ __forceinline__ void layer_body(const LayerArgs &a, int ktiles_rt = 0) {
+  const int ktiles = LONG ? ktiles_rt : WNK / 16;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float *prm = reinterpret_cast<float *>(lds + NBUF * CHUNK_BYTES);   // bq bk bv | bo | b1 | b2 | ln1w ln1b ln2w ln2b
   const Geo &G = a.g;
@@ -953,7 +945,7 @@ __device__ __forceinline__ void layer_body(const LayerArgs &a) {
     const bool rowok = r < G.N;
     const int n_ck = a.kcnt[2 * b], n_ak = a.kcnt[2 * b + 1];
     const bool isq = rc < G.P && !is_ctx(G, b, rc);
-    const u32x4 *kv = a.KV + (long)b * KV_EP + lane;
+    const u32x4 *kv = a.KV + (LONG ? (long)b * (ktiles >> 2) : (long)b) * KV_EP + lane;
     const int nkt = __builtin_amdgcn_readfirstlane((n_ak + 15) >> 4);     // (uniform per wave: one episode per tile)
     X3_LAP(st, 7);
 
@@ -984,7 +976,14 @@ __device__ __forceinline__ void layer_body(const LayerArgs &a) {
       // (head 0's K / V pairs are requested before the epilogue of the Q projection and land while it runs)
       if (nkt <= 1) { HeadKV<1> k0; k0.load(kv, 0); q_epilogue(); attention_tile<1>(qh, ql, kv, nv, k0); }
       else if (nkt == 2) { HeadKV<2> k0; k0.load(kv, 0); q_epilogue(); attention_tile<2>(qh, ql, kv, nv, k0); }
-      else { HeadKV<4> k0; k0.load(kv, 0); q_epilogue(); attention_tile<4>(qh, ql, kv, nv, k0); }
+      else if (!LONG || nkt <= 4) { HeadKV<4> k0; k0.load(kv, 0); q_epilogue(); attention_tile<4>(qh, ql, kv, nv, k0); }
+#if X3_LONGKEYS
+      else if constexpr (LONG) {
+        if (nkt <= 6) { u32x4 k0[LK_UNIT]; long_unit_load<6>(k0, kv, 0); q_epilogue(); attention_long<6>(qh, ql, kv, nv, k0); }
+        else if (nkt <= 8) { u32x4 k0[LK_UNIT]; long_unit_load<8>(k0, kv, 0); q_epilogue(); attention_long<8>(qh, ql, kv, nv, k0); }
+        else { u32x4 k0[LK_UNIT]; long_unit_load<10>(k0, kv, 0); q_epilogue(); attention_long<10>(qh, ql, kv, nv, k0); }
+      }
+#endif
       X3_LAP(st, 6);
     }
     const long srow = (long)b * G.N + rc;          // (SAVE) fp32 row of this lane's token
@@ -1069,8 +1068,8 @@ __device__ __forceinline__ void layer_body(const LayerArgs &a) {
         a.zimg[xpiece(zr >> 4, ks, 1, 16 * g + (int)(zr & 15))] = __builtin_bit_cast(u32x4, ol);
       }
       if (!LAST && kp >= 0) {
-        a.KXout[xpiece((long)b * (WNK / 16) + (kp >> 4), ks, 0, 16 * g + (kp & 15))] = __builtin_bit_cast(u32x4, oh);
-        a.KXout[xpiece((long)b * (WNK / 16) + (kp >> 4), ks, 1, 16 * g + (kp & 15))] = __builtin_bit_cast(u32x4, ol);
+        a.KXout[xpiece((long)b * ktiles + (kp >> 4), ks, 0, 16 * g + (kp & 15))] = __builtin_bit_cast(u32x4, oh);
+        a.KXout[xpiece((long)b * ktiles + (kp >> 4), ks, 1, 16 * g + (kp & 15))] = __builtin_bit_cast(u32x4, ol);
       }
     }
     load_tile(a.XIN, tn, ln, xh, xl);       // (after the last round: the same tile once more, from L2, dropped)
@@ -1093,6 +1092,11 @@ __global__ __launch_bounds__(THREADS) void layer_kernel(LayerArgs a) { layer_bod
 // the same layer with the fp32 side outputs the per-op backward reads (LayerArgs.sv*): its forward recompute at the speed of the
 // rollout's own kernel instead of four generic GEMMs, two LayerNorm kernels and the attention kernel per layer
 __global__ __launch_bounds__(THREADS) void layer_save_kernel(LayerArgs a) { layer_body<false, true>(a); }
+#if X3_LONGKEYS
+// the layer on the long-key layout: a rollout that shows an episode 65 .. NK_MAX keys (every step of it, also those with few keys)
+template <bool LAST>
+__global__ __launch_bounds__(THREADS) X3_NO_PK_F32 void layer_long_kernel(LayerArgs a, int ktiles) { layer_body<LAST, false, true>(a, ktiles); }
+#endif
 
 // ---- acquisition head (NOUT = 1, model/head.py:27-33) / one GMM head (NOUT = 3, model/head.py:152-186) --------------
 // out[row * out_stride + out_off + j] = w2[j] . relu(W1 z + b1) + b2[j] over the 16-row tiles of an image

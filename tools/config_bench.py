@@ -3,6 +3,8 @@
 cfg1 al_mix dx=1 B=8 T=5 nq=32 | cfg2 location B=1000 T=30 nq=200 (d=32 and d=256/F=1024/H=8 bf16) |
 cfg3 al_mix dx=2 B=512 (one GPU's share of 4096) T=50 nq=200, split mask | cfg5 psychometric d=512 H=8 predefined
 mask T=30 nq=200 (F=128 literal config and F=2048).  cfg4 (CES EIG) is tools/eig_bench.py.
+--configs 3w [--pairs N]: cfg3's geometry at d=256/F=1024/H=8 f16x3 (153 keys: the long-key variants of the x3 path), N alternating
+pairs of the x3 path and the generic pipeline (ALINE_DISABLE_X3) in one process, one JSON line per pair.
 Random-init weights, synthetic task data, sampled designs, HIP-graph replay; which kernel path ran is reported."""
 import argparse
 import json
@@ -17,7 +19,7 @@ from aline_amd import Aline, Embedder, Encoder, OutputHead  # noqa: E402
 from aline_amd.rollout import Rollout  # noqa: E402
 from aline_amd.tasks import GPTask, HiddenLocation, PsychometricTask  # noqa: E402
 from aline_amd.utils import create_target_mask  # noqa: E402
-from bench import PEAK_BF16_DENSE_TFLOPS, PEAK_F32_MFMA_TFLOPS, algorithmic_flops_per_episode  # noqa: E402
+from bench import PEAK_BF16_DENSE_TFLOPS, PEAK_F32_MFMA_TFLOPS, HipEvents, algorithmic_flops_per_episode, x3_layer_flops  # noqa: E402
 
 # MFMA passes a product costs on the f16/bf16 pipe, by arithmetic policy (f32 runs on the fp32 MFMA instead)
 PASSES = {"bf16": 1, "bf16x3": 3, "f16x3": 3}
@@ -31,7 +33,7 @@ def build(dx, d, F, H, n_theta, emb, precision):
 def path_of(d, F, H, emb, precision, keys):
     if precision == "f32" and (d, F, H) == (32, 128, 4) and emb == "theta":
         return "fused::rollout_f32_kernel"
-    if precision == "f16x3" and d == 256 and H == 8 and keys <= 64:
+    if precision == "f16x3" and d == 256 and H == 8 and keys <= 160:
         return "x3::layer_kernel"
     if precision == "f16x3" and d == 512 and H == 8 and keys <= 64:
         return "x5::layer_kernel"
@@ -78,11 +80,55 @@ def run(name, model, batch, T, steps, meta):
     print(json.dumps(out), flush=True)
 
 
+def timed_replays(ro, steps):
+    ro.refresh_uniform(); ro.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        ro.refresh_uniform()
+        ro.replay()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def run_pairs(name, model, batch, T, steps, pairs, geo):
+    """Same-box alternating pairs: ms per graph-replayed rollout on the x3 path and on the generic pipeline (the same library with
+    ALINE_DISABLE_X3), then the x3 path's layer-kernel launch (the C ABI's event pair: last layer of the last step) and its fraction
+    of the f16 matrix pipe's peak on the SURVEY 8-d FLOPs of that launch."""
+    from aline_amd import _lib
+    ros, paths = {}, {}
+    for key, env in (("x3", {}), ("generic", {"ALINE_DISABLE_X3": "1"})):
+        with _lib.debug_env(env):
+            ros[key] = Rollout(model, batch, T, select="sample", keep_zt=False, keep_posterior=True)
+            ros[key].run()
+            torch.cuda.synchronize()
+            paths[key] = ros[key].path
+            ros[key].capture()              # (the graph holds this path's kernels: replays need no switch)
+    for i in range(pairs):
+        ms = {key: timed_replays(ros[key], steps) for key in ("x3", "generic")}
+        print(json.dumps({"config": name, "pair": i, "B": ros["x3"].B, "T": T, "x3_ms_per_rollout": round(ms["x3"], 3),
+                          "generic_ms_per_rollout": round(ms["generic"], 3), "ratio": round(ms["generic"] / ms["x3"], 3), "paths": paths,
+                          "kernel": ros["x3"].kernel_name}), flush=True)
+    ro, ev = ros["x3"], HipEvents()
+    ro.r.ev_kernel_start, ro.r.ev_kernel_stop = ev.a, ev.b
+    ks = []
+    for _ in range(3):
+        ro.refresh_uniform(); ro.run(); torch.cuda.synchronize()
+        ks.append(ev.elapsed_ms())
+    k = sum(ks) / len(ks)
+    fl = x3_layer_flops(geo["d"], geo["F"], geo["n_c0"] + T - 1, geo["n_q0"] - (T - 1), geo["n_td"] + geo["n_th"], geo["n_s"]) * ro.B
+    print(json.dumps({"config": name, "kernel": ro.kernel_name, "layer_kernel_us": round(k * 1e3, 1),
+                      "frac_of_peak": round(fl / (k * 1e-3) / (PEAK_BF16_DENSE_TFLOPS * 1e12), 4),
+                      "frac_executed": round(3 * fl / (k * 1e-3) / (PEAK_BF16_DENSE_TFLOPS * 1e12), 4),
+                      "range": ro.range_status()}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="1,2,3,5")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--precs", default="", help="comma list: only these precisions (default: all)")
+    ap.add_argument("--pairs", type=int, default=5, help="3w: alternating pairs")
     args = ap.parse_args()
     global ONLY_PRECS
     ONLY_PRECS = set(args.precs.split(",")) if args.precs else None
@@ -118,6 +164,14 @@ def main():
         for prec in ("f32", "f16x3"):
             run(f"cfg3 al_mix dx=2 B=512 (of 4096 over 8 GPUs) T=50, split mask (data) {prec}", build(2, 32, 128, 4, 3, "mix", prec),
                 batch, 50, args.steps, {"d": 32, "precision": prec, "path": path_of(32, 128, 4, "mix", prec, 999), "geo": geo})
+    if "3w" in want:
+        task = GPTask(dim_x=2, embedding_type="mix", n_context_init=1, n_query_init=200, n_target_theta=3,
+                      n_target_data=100, device=dev)
+        batch = task.sample_batch(512)
+        batch["target_mask"] = create_target_mask("split", "mix", 100, 3, None, None, None, None, "data")
+        geo = dict(dx=2, dy=1, d=256, F=1024, H=8, L=3, C=10, n_c0=1, n_q0=200, n_td=100, n_th=3, n_s=100, embedding_type="mix")
+        run_pairs("cfg3 geometry at d=256 F=1024 H=8 f16x3: al_mix dx=2 B=512 T=50, split mask (data)", build(2, 256, 1024, 8, 3, "mix", "f16x3"),
+                  batch, 50, args.steps, args.pairs, geo)
     if "5" in want:
         task = PsychometricTask(n_query_init=200, n_context_init=1, device=dev)
         batch = task.sample_batch(256)
