@@ -110,6 +110,19 @@ Plan make_plan(const aline_model &m, int B, int P, int n_td, int ey_rows, bool q
     p.xRaw = take((size_t)T * B * n_t * kRawStride);
     p.xRawQ = take(query_gmm ? (size_t)B * tpe * 16 * kRawStride : 0);       // raw GMM outputs of every token row of ONE step (posterior_out_query)
   }
+  if (T > 0 && m.d == x1::D && m.precision == ALINE_PREC_F16X3) {           // x1 path (x1.h): the same buffers at d = 128, one block of 64 keys
+    const size_t tpe = (N + 15) / 16, img = (size_t)x1::img_pieces((long)B * tpe) * 4;
+    p.xImg = take((size_t)x1::image_words(m.L, m.F, m.C));
+    p.xIn = take(img); p.xA = take(img); p.xB = take(img);
+    p.xKV = take((size_t)B * x1::KV_EP * 4);
+    p.xKeys = take((size_t)B * x1::WNK); p.xKcnt = take((size_t)B * 2);
+    p.xKX = take((size_t)x1::img_pieces((long)B * (x1::WNK / 16)) * 4);
+    p.xKpos = take((size_t)B * tpe * 16 / 2 + 1);
+    p.xLog = take((size_t)B * tpe * 16);
+    p.xZimg = take((size_t)x1::img_pieces(((long)T * B * n_t + 15) / 16) * 4);
+    p.xRaw = take((size_t)T * B * n_t * kRawStride);
+    p.xRawQ = take(query_gmm ? (size_t)B * tpe * 16 * kRawStride : 0);
+  }
   if (T > 0 && m.d == s3::D && m.precision == ALINE_PREC_F16X3) {           // s3 path (s3.h): d = 32 split-f16 tile images
     const size_t tpe = (N + 15) / 16, img = (size_t)s3::img_pieces((long)B * tpe) * 4;
     p.sImg = take((size_t)s3::image_words(m.L, m.F, m.C));
@@ -945,6 +958,8 @@ static int rollout_fused(const aline_model *m, const aline_rollout *r, void *ws,
 extern "C++" {
 #define X3_NS x3
 #define X3_LONGKEYS 1
+#define X3_PAIRED 0
+#define X3_DBG_DISABLE ALINE_DBG_DISABLE_X3
 #include "x3_host.h"
 #undef X3_NS
 #undef X3_LONGKEYS
@@ -952,7 +967,16 @@ extern "C++" {
 #define X3_LONGKEYS 0
 #include "x3_host.h"
 #undef X3_NS
+#undef X3_PAIRED
+#undef X3_DBG_DISABLE
+#define X3_NS x1
+#define X3_PAIRED 1
+#define X3_DBG_DISABLE ALINE_DBG_DISABLE_X1
+#include "x3_host.h"
+#undef X3_NS
 #undef X3_LONGKEYS
+#undef X3_PAIRED
+#undef X3_DBG_DISABLE
 }
 
 // The s3 path (s3.h): d = 32 / 4 heads at reference precision, any embedding mode, up to 160 keys per episode -- one
@@ -1082,6 +1106,7 @@ int aline_rollout_path(const aline_model *m, const aline_rollout *r) {
   if (fused_eligible(*m, *r)) return ALINE_PATH_FUSED;
   if (x3::eligible(*m, *r)) return ALINE_PATH_X3;
   if (x5::eligible(*m, *r)) return ALINE_PATH_X5;
+  if (x1::eligible(*m, *r)) return ALINE_PATH_X1;
   if (s3_eligible(*m, *r)) return ALINE_PATH_S3;
   return ALINE_PATH_GENERIC;
 }
@@ -1106,6 +1131,7 @@ int aline_rollout_kernel_name(const aline_model *m, const aline_rollout *r, char
     case ALINE_PATH_FUSED: snprintf(buf, n, "fused::rollout_f32_kernel<%s>", dbg(ALINE_DBG_FUSED_STAMPS) ? "true" : "false"); break;
     case ALINE_PATH_X3: snprintf(buf, n, x3::long_keys(*m, *r) ? "x3::layer_long_kernel<true>" : "x3::layer_kernel<true>"); break;      // (the launch the event pair brackets: last layer of the last step)
     case ALINE_PATH_X5: snprintf(buf, n, "x5::layer_kernel<true>"); break;
+    case ALINE_PATH_X1: snprintf(buf, n, "x1::layer_kernel<true>"); break;
     case ALINE_PATH_S3: {
       const S3Shape sh = s3_shape(*m, *r);
       snprintf(buf, n, "s3::step_kernel<%d, %d, %d, false, %s>", m->F, sh.nw, sh.nw == 8 ? s3::NKP_MAX : 2,
@@ -1123,6 +1149,7 @@ int aline_rollout_forward(const aline_model *m, const aline_rollout *r, void *ws
     case ALINE_PATH_FUSED: return rollout_fused(m, r, ws, ws_bytes, stream);
     case ALINE_PATH_X3: return x3::rollout(m, r, ws, ws_bytes, stream);
     case ALINE_PATH_X5: return x5::rollout(m, r, ws, ws_bytes, stream);
+    case ALINE_PATH_X1: return x1::rollout(m, r, ws, ws_bytes, stream);
     case ALINE_PATH_S3: return rollout_s3(m, r, ws, ws_bytes, stream);
     default: break;     /* generic pipeline (its entry points report invalid arguments) */
   }

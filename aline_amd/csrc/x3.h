@@ -4,6 +4,9 @@
 //   namespace x5: d = 512, 8 heads of 64 (config/task/psychometric.yaml with d_model = 512): a token tile's input fragments (128
 //                 registers) and accumulators (128) do not fit a 256-register wave, so a workgroup is 4 waves -- one per SIMD --
 //                 with the whole 512-entry register file of their SIMD lane (accumulators in the AGPR half).
+//   namespace x1: d = 128, 4 heads of 32 (the first width above the reference's d = 32): the images, the key list, the weight stream
+//                 and the attention of x3_impl.h at this width; a k-step is half a 16-pair chunk, so the weight layout and the
+//                 kernels that walk it are x1.h's (X3_PAIRED): 8 waves per workgroup, TWO token tiles per wave.
 #pragma once
 #include "tile_image.h"
 
@@ -25,6 +28,7 @@
 #define X3_ILV256 1
 #endif
 #define X3_INTERLEAVE X3_ILV256
+#define X3_PAIRED 0
 #include "x3_impl.h"
 #undef X3_NS
 #undef X3_D
@@ -33,6 +37,7 @@
 #undef X3_KV_AHEAD
 #undef X3_LONGKEYS
 #undef X3_INTERLEAVE
+#undef X3_PAIRED
 
 #define X3_NS x5
 #define X3_D 512
@@ -47,6 +52,7 @@
 #define X3_ILV512 1
 #endif
 #define X3_INTERLEAVE X3_ILV512
+#define X3_PAIRED 0
 #include "x3_impl.h"
 #undef X3_NS
 #undef X3_D
@@ -55,3 +61,22 @@
 #undef X3_KV_AHEAD
 #undef X3_LONGKEYS
 #undef X3_INTERLEAVE
+#undef X3_PAIRED
+
+#define X3_NS x1
+#define X3_D 128
+#define X3_HD 32
+#define X3_THREADS 512
+#define X3_KV_AHEAD 1
+#define X3_LONGKEYS 0      // (64 keys at most)
+#define X3_INTERLEAVE 1
+#define X3_PAIRED 1
+#include "x3_impl.h"
+#undef X3_NS
+#undef X3_D
+#undef X3_HD
+#undef X3_THREADS
+#undef X3_KV_AHEAD
+#undef X3_LONGKEYS
+#undef X3_INTERLEAVE
+#undef X3_PAIRED

@@ -1,5 +1,6 @@
 // Host side of the split-f16 tile-image paths (x3_impl.h): eligibility and the per-rollout launch sequence.  Included by
-// aline_hip.hip once per width (namespace X3_NS = x3: d = 256, x5: d = 512), after Ctx / Plan / the shared launch helpers.
+// aline_hip.hip once per width (namespace X3_NS = x3: d = 256, x5: d = 512, x1: d = 128 -- X3_PAIRED, the kernels of x1.h), after
+// Ctx / Plan / the shared launch helpers.  X3_DBG_DISABLE: the bit of the diagnostic word that switches the path off.
 namespace X3_NS {
 
 template <int NOUT>
@@ -33,6 +34,7 @@ static int pack_weights(const aline_model &mm, unsigned *img, unsigned *range_fl
   return ALINE_OK;
 }
 
+#if !X3_PAIRED
 // ---- forward recompute of the training backward (round 4) -----------------------------------------------------------------
 // The per-op backward of a d = 256 / 512 model needs, per layer, the attention output, both LayerNorm inputs and outputs and the
 // hidden units of every (step, episode) INSTANCE of a chunk.  It used to recompute them with the generic kernels (four GEMMs, the
@@ -99,13 +101,14 @@ static int recompute(const aline_model *m, const Geo &g, int max_keys, const flo
   }
   return ALINE_OK;
 }
+#endif
 
 // Eligibility of the tile-image path of this width (x3: d = 256 / 8 heads of 32, x5: d = 512 / 8 heads of 64) at reference
 // precision -- every product a 3-term f16 split on the matrix pipe.  Up to NK_MAX visible keys per episode: 64, or 160 where the
 // width has the long-key variants (x3), which a rollout takes as a whole iff some step of it shows more than 64 (long_keys()).
 static int max_keys(const aline_model &m, const aline_rollout &r) { return r.n_ctx0 + r.T - 1 + r.n_target_data + m.n_theta; }
 static bool eligible(const aline_model &m, const aline_rollout &r) {
-  if (dbg(ALINE_DBG_DISABLE_X3)) return false;
+  if (dbg(X3_DBG_DISABLE)) return false;
   if (m.precision != ALINE_PREC_F16X3 || m.d != D || m.H != H || m.F % 32) return false;
   if (max_keys(m, r) > NK_MAX) return false;
   if ((size_t)NBUF * CHUNK_BYTES + (size_t)std::max(layer_params(m.F), head_lds_params(m.F)) * 4 > 160 * 1024) return false;
@@ -147,7 +150,9 @@ static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_layer);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_layer);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+#if !X3_PAIRED
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+#endif
   const int cus = device_cus();
   // the layout of the episode's keys (x3_impl.h, KV_EP): c.pl sized the key list, the key image and the K / V buffer for these groups
   const int ktiles = 4 * c.pl.xGroups;
@@ -178,6 +183,9 @@ static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_
       KvArgs ka{};
       ka.g = c.g; ka.tpe = tpe; ka.nkt2 = nkt2; ka.X = KX; ka.img = img + l * lw; ka.F = F; ka.keyrow = keyrow; ka.kcnt = kcnt; ka.KV = KV;
       ka.ngroups = (int)(((long)r->B * nkt2 + WAVES - 1) / WAVES);
+#if X3_PAIRED
+      hipLaunchKernelGGL(kv_all_kernel, dim3((unsigned)std::min(ka.ngroups, cus)), dim3(THREADS), smem_kv, c.st, ka);
+#else
       // (groups of key tiles that do not fill the chip: one job -- K | V x channel half -- per workgroup, so that every CU streams)
       constexpr int NJ = 2 * CPK;
       const bool split = (ka.ngroups * NJ + cus - 1) / cus < NJ * ((ka.ngroups + cus - 1) / cus);      // fewer chunk passes per CU when split
@@ -189,9 +197,10 @@ static int rollout(const aline_model *m, const aline_rollout *r, void *ws, size_
 #endif
       if (split) hipLaunchKernelGGL(kv_split_kernel, kv_grid, dim3(THREADS), smem_kv, c.st, ka);
       else hipLaunchKernelGGL(kv_all_kernel, kv_grid, dim3(THREADS), smem_kv, c.st, ka);
+#endif
       CHECK_LAUNCH();
       LayerArgs la{};
-      la.g = c.g; la.tpe = tpe; la.ngroups = (int)((tiles + WAVES - 1) / WAVES);
+      la.g = c.g; la.tpe = tpe; la.ngroups = (int)((layer_units(r->B, tpe) + WAVES - 1) / WAVES);
       la.XIN = xin; la.XOUT = xout; la.img = img + l * lw; la.F = F; la.KV = KV; la.kcnt = kcnt; la.range_flag = c.flag(); la.keypos = keypos; la.KXout = KX;
       const bool last = l == m->L - 1;
       la.zimg = (last && want_gmm) ? Zimg : nullptr; la.zrow0 = (long)t * r->B * n_t;

@@ -21,7 +21,8 @@
 //                  registers: 8 waves x one 16-token tile, weights streamed through LDS by LDS-DMA (32 KB chunks
 //                  of 16 pairs, 3 buffers); persistent workgroups walk the tile list, the weight stream is cyclic
 //   head_kernel    acquisition logits / one GMM head (hidden layer in registers, [F -> 1|3] in fp32 FMA)
-// (no include guard: x3.h includes this file once per width, with X3_NS / X3_D / X3_HD / X3_THREADS set)
+// (no include guard: x3.h includes this file once per width, with X3_NS / X3_D / X3_HD / X3_THREADS set.  X3_PAIRED, d = 128: the
+//  images, the key list, the stream and the attention below at that width; the weight layout and the kernels that walk it are x1.h's)
 
 namespace X3_NS {
 
@@ -35,9 +36,11 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int D = X3_D, HD = X3_HD, H = D / HD, NMT = D / 16, NKS = D / 32, WNK = 64;
 constexpr int KPH = HD / 32, MPH = HD / 16;           // k-steps / 16-channel tiles of one head
+#if !X3_PAIRED
 constexpr int CPK = NMT / 16;                         // chunks per k-step of a product with D outputs (16 pairs per chunk)
 constexpr int PC = NKS * CPK;                         // chunks of a D x D product
 constexpr int W1C = NKS / 8;                          // chunks of the W1 pairs of 32 hidden units (2 tiles x NKS k-steps)
+#endif                                                // (X3_PAIRED, d = 128: a k-step is half a chunk -- the chunk layout of x1.h)
 constexpr int THREADS = X3_THREADS, WAVES = THREADS / 64;
 constexpr int CHUNK_PAIRS = 16, CHUNK_BYTES = CHUNK_PAIRS * 2048, CHUNK_WORDS = CHUNK_BYTES / 4;
 constexpr int NBUF = 4, PD = 3;                       // LDS ring, chunks issued ahead of the one in use
@@ -117,6 +120,7 @@ __device__ __forceinline__ float group_max4(float v, float inf) {
 __host__ __device__ inline long img_pieces(long tiles) { return tiles * (NKS * 2 * 64); }
 __device__ __forceinline__ long xpiece(long tile, int ks, int hl, int lane) { return ((tile * NKS + ks) * 2 + hl) * 64 + lane; }
 
+#if !X3_PAIRED
 // weight image of a layer (32-bit words): chunks [Q PC][K PC][V PC][OUT PC][FFN: per 32 hidden units W1 (W1C chunks) | W2 (CPK)],
 // then fp32 parameters bq (pre-scaled) bk bv | bo | b1 | b2 | ln1w ln1b ln2w ln2b.  A chunk is 16 fragment pairs; chunk c of a
 // product with D outputs holds k-step c / CPK, output tiles 16 (c % CPK) + p; pair q = 16 j + p of a W1 group: k-step q >> 1,
@@ -130,6 +134,8 @@ __host__ __device__ inline int head_params(int F) { return 4 * F + 4; }
 __host__ __device__ inline int head_lds_params(int F) { return 4 * F; }
 __host__ __device__ inline long head_words(int F) { return (long)head_chunks(F) * CHUNK_WORDS + head_params(F); }
 __host__ __device__ inline long image_words(int L, int F, int C) { return (long)L * layer_words(F) + (long)(1 + C) * head_words(F); }
+__host__ __device__ inline long layer_units(long B, int tpe) { return B * tpe; }      // work units of the layer kernel: token tiles
+#endif
 
 struct PackArgs {
   int L, F, C;
@@ -154,6 +160,7 @@ __device__ __forceinline__ unsigned pair_word(const float *W, int K, int row0, i
   return hl ? lo : hi;
 }
 
+#if !X3_PAIRED
 __global__ void pack_kernel(PackArgs a) {
   const long lw = layer_words(a.F), hw = head_words(a.F), total = image_words(a.L, a.F, a.C);
   const float qscale = rsqrtf((float)HD) * 1.44269504088896340736f;   // softmax runs in exp2
@@ -207,6 +214,7 @@ __global__ void pack_kernel(PackArgs a) {
     a.out[i] = v;
   }
 }
+#endif
 
 // ---- X0 image from the cached fp32 point embeddings (model/embedder.py:128-214): Ex (+ Ey on context rows), theta
 // tokens; rows beyond N of an episode's last tile are zero.  One thread = one (piece hi, piece lo).
@@ -564,6 +572,7 @@ __device__ __forceinline__ void idle_chunks(St &st, int nchunks) {
     st.sync();
   }
 }
+#if !X3_PAIRED
 // FFN-shaped run over F/32 groups of 32 hidden units: W1C chunks = the group's W1 pairs (pair q: k-step q >> 1, hidden tile
 // q & 1) -> hidden units in registers; CPK chunks = the group's W2 pairs -> consume(c, output tile, A_hi, A_lo) with the hidden
 // fragment pair made by `hidden(c, h0, h1)`.  Fragment prefetch runs across all chunk boundaries of the run.
@@ -593,6 +602,8 @@ __device__ __forceinline__ void ffn_run(St &st, FragRing &r, int ngroups, const 
     }
   }
 }
+
+#endif
 
 __device__ __forceinline__ void load_tile(const u32x4 *X, long tile, int lane_idx, f16x8 (&xh)[NKS], f16x8 (&xl)[NKS]) {
 #pragma unroll
@@ -651,6 +662,7 @@ struct KvArgs {
 };
 
 // kv_all_kernel / kv_split_kernel, and their variants on the long-key layout
+#if !X3_PAIRED
 #define X3_KV_LONG 0
 #include "x3_kv.h"
 #undef X3_KV_LONG
@@ -658,6 +670,7 @@ struct KvArgs {
 #define X3_KV_LONG 1
 #include "x3_kv.h"
 #undef X3_KV_LONG
+#endif
 #endif
 
 // ---- one encoder layer of a token tile ----------------------------------------------------------------------------
@@ -880,6 +893,7 @@ __device__ __forceinline__ void attention_long(f16x8 (&qh)[NKS], f16x8 (&ql)[NKS
 }
 #endif
 
+#if !X3_PAIRED
 // fp32 side outputs of layer_save_kernel: written once, read by other kernels much later -- streaming stores
 __device__ __forceinline__ void sv_store(float *p, const f32x4 &v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(p)); }
 
@@ -1097,6 +1111,7 @@ __global__ __launch_bounds__(THREADS) void layer_save_kernel(LayerArgs a) { laye
 template <bool LAST>
 __global__ __launch_bounds__(THREADS) X3_NO_PK_F32 void layer_long_kernel(LayerArgs a, int ktiles) { layer_body<LAST, false, true>(a, ktiles); }
 #endif
+#endif
 
 // ---- acquisition head (NOUT = 1, model/head.py:27-33) / one GMM head (NOUT = 3, model/head.py:152-186) --------------
 // out[row * out_stride + out_off + j] = w2[j] . relu(W1 z + b1) + b2[j] over the 16-row tiles of an image
@@ -1106,6 +1121,7 @@ struct HeadArgs {
   float *out; int out_stride, out_off;
   float tau;      // acquisition head with a time token: this step's t / T (b1 + tau W1[:, d] is the hidden layer's bias), else 0
 };
+#if !X3_PAIRED
 template <int NOUT>
 __global__ __launch_bounds__(THREADS) void head_kernel(HeadArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1169,5 +1185,8 @@ __global__ __launch_bounds__(THREADS) void head_kernel(HeadArgs a) {
   }
   st.finish();
 }
+#else
+#include "x1.h"      // d = 128: weight layout, pack / K-V / layer / head kernels of the two-tile wave
+#endif
 
 }  // namespace X3_NS

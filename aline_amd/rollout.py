@@ -109,7 +109,7 @@ class Rollout:
         self._acts_stamp = None         # (write generation of saved_acts, library diagnostic state) of this rollout's last forward
 
     PATHS = {0: "generic pipeline", 1: "fused::rollout_f32_kernel",
-             3: "x3::layer_kernel", 4: "s3::step_kernel", 5: "x5::layer_kernel"}
+             3: "x3::layer_kernel", 4: "s3::step_kernel", 5: "x5::layer_kernel", 6: "x1::layer_kernel"}
 
     @property
     def path(self):

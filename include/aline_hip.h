@@ -188,7 +188,8 @@ enum { ALINE_PATH_GENERIC = 0,   /* stage kernels + GEMMs, any configuration */
        /* 2: the bf16 `wide` path of rounds 1-3 (NLL error 2e-2; removed in ABI 5: BF16 models run the generic pipeline) */
        ALINE_PATH_X3 = 3,        /* x3.h: d = 256, F16X3 (reference precision on the f16 matrix pipe) */
        ALINE_PATH_S3 = 4,        /* s3.h: d = 32, F16X3, any embedding mode, one launch per design step */
-       ALINE_PATH_X5 = 5 };      /* x3.h, namespace x5: d = 512 / 8 heads of 64, F16X3 (the psychometric configuration's width) */
+       ALINE_PATH_X5 = 5,        /* x3.h, namespace x5: d = 512 / 8 heads of 64, F16X3 (the psychometric configuration's width) */
+       ALINE_PATH_X1 = 6 };      /* x1.h: d = 128 / 4 heads of 32, F16X3, up to 64 visible keys: two token tiles per wave */
 int aline_rollout_path(const aline_model *m, const aline_rollout *r);
 size_t aline_rollout_saved_acts_bytes(const aline_model *m, const aline_rollout *r);   /* see aline_rollout.saved_acts */
 /* Name (as rocprofv3 prints it, template arguments included) of the dominant kernel of that path for (m, r) -- the launch
@@ -321,6 +322,7 @@ enum { ALINE_DBG_DISABLE_FUSED = 1u << 0,      /* fused::rollout_f32_kernel off 
        ALINE_DBG_NO_BWD_KV_SPARSE = 1u << 12,  /* per-op backward: the in-projection's gradient products over all rows x all 3 d columns (dK / dV of the non-key rows are zeros) */
        ALINE_DBG_SELECT_WORKGROUP = 1u << 13,  /* design selection: the workgroup-per-episode kernel also where one wave per episode would do */
        ALINE_DBG_S3_SELECT_KERNEL = 1u << 14,  /* s3 path: the design selection as a launch of its own (acq_select_wave_kernel) instead of inside the step kernel */
+       ALINE_DBG_DISABLE_X1 = 1u << 15,        /* x1 path (d = 128) off -> generic pipeline on the F16X3 GEMM policy */
        /* backward: switch ONE fused kernel back to the per-op pipeline it replaces */
        ALINE_DBG_NO_BWD_TAIL = 1u << 16, ALINE_DBG_NO_BWD_ATTN_BLOCK = 1u << 17, ALINE_DBG_NO_BWD_ACQ = 1u << 18,
        ALINE_DBG_NO_BWD_LAYER_FWD = 1u << 19, ALINE_DBG_NO_BWD_LAYER_FWD_FLAT = 1u << 20,

@@ -5,6 +5,8 @@ cfg3 al_mix dx=2 B=512 (one GPU's share of 4096) T=50 nq=200, split mask | cfg5 
 mask T=30 nq=200 (F=128 literal config and F=2048).  cfg4 (CES EIG) is tools/eig_bench.py.
 --configs 3w [--pairs N]: cfg3's geometry at d=256/F=1024/H=8 f16x3 (153 keys: the long-key variants of the x3 path), N alternating
 pairs of the x3 path and the generic pipeline (ALINE_DISABLE_X3) in one process, one JSON line per pair.
+--configs 1w [--pairs N]: the headline geometry (location_finding B=1000 T=30 nq=200) at d=128/F=512/H=4 f16x3, the same pairs for the
+x1 path (ALINE_DISABLE_X1).
 Random-init weights, synthetic task data, sampled designs, HIP-graph replay; which kernel path ran is reported."""
 import argparse
 import json
@@ -37,6 +39,8 @@ def path_of(d, F, H, emb, precision, keys):
         return "x3::layer_kernel"
     if precision == "f16x3" and d == 512 and H == 8 and keys <= 64:
         return "x5::layer_kernel"
+    if precision == "f16x3" and d == 128 and H == 4 and keys <= 64:
+        return "x1::layer_kernel"
     return "generic pipeline"
 
 
@@ -91,25 +95,25 @@ def timed_replays(ro, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def run_pairs(name, model, batch, T, steps, pairs, geo):
-    """Same-box alternating pairs: ms per graph-replayed rollout on the x3 path and on the generic pipeline (the same library with
-    ALINE_DISABLE_X3), then the x3 path's layer-kernel launch (the C ABI's event pair: last layer of the last step) and its fraction
+def run_pairs(name, model, batch, T, steps, pairs, geo, key="x3"):
+    """Same-box alternating pairs: ms per graph-replayed rollout on the x3 (key = "x1": x1) path and on the generic pipeline (the same
+    library with ALINE_DISABLE_X3 / _X1), then the path's layer-kernel launch (the C ABI's event pair: last layer of the last step) and its fraction
     of the f16 matrix pipe's peak on the SURVEY 8-d FLOPs of that launch."""
     from aline_amd import _lib
     ros, paths = {}, {}
-    for key, env in (("x3", {}), ("generic", {"ALINE_DISABLE_X3": "1"})):
+    for k, env in ((key, {}), ("generic", {f"ALINE_DISABLE_{key.upper()}": "1"})):
         with _lib.debug_env(env):
-            ros[key] = Rollout(model, batch, T, select="sample", keep_zt=False, keep_posterior=True)
-            ros[key].run()
+            ros[k] = Rollout(model, batch, T, select="sample", keep_zt=False, keep_posterior=True)
+            ros[k].run()
             torch.cuda.synchronize()
-            paths[key] = ros[key].path
-            ros[key].capture()              # (the graph holds this path's kernels: replays need no switch)
+            paths[k] = ros[k].path
+            ros[k].capture()              # (the graph holds this path's kernels: replays need no switch)
     for i in range(pairs):
-        ms = {key: timed_replays(ros[key], steps) for key in ("x3", "generic")}
-        print(json.dumps({"config": name, "pair": i, "B": ros["x3"].B, "T": T, "x3_ms_per_rollout": round(ms["x3"], 3),
-                          "generic_ms_per_rollout": round(ms["generic"], 3), "ratio": round(ms["generic"] / ms["x3"], 3), "paths": paths,
-                          "kernel": ros["x3"].kernel_name}), flush=True)
-    ro, ev = ros["x3"], HipEvents()
+        ms = {k: timed_replays(ros[k], steps) for k in (key, "generic")}
+        print(json.dumps({"config": name, "pair": i, "B": ros[key].B, "T": T, f"{key}_ms_per_rollout": round(ms[key], 3),
+                          "generic_ms_per_rollout": round(ms["generic"], 3), "ratio": round(ms["generic"] / ms[key], 3), "paths": paths,
+                          "kernel": ros[key].kernel_name}), flush=True)
+    ro, ev = ros[key], HipEvents()
     ro.r.ev_kernel_start, ro.r.ev_kernel_stop = ev.a, ev.b
     ks = []
     for _ in range(3):
@@ -128,7 +132,7 @@ def main():
     ap.add_argument("--configs", default="1,2,3,5")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--precs", default="", help="comma list: only these precisions (default: all)")
-    ap.add_argument("--pairs", type=int, default=5, help="3w: alternating pairs")
+    ap.add_argument("--pairs", type=int, default=5, help="3w / 1w: alternating pairs")
     args = ap.parse_args()
     global ONLY_PRECS
     ONLY_PRECS = set(args.precs.split(",")) if args.precs else None
@@ -172,6 +176,11 @@ def main():
         geo = dict(dx=2, dy=1, d=256, F=1024, H=8, L=3, C=10, n_c0=1, n_q0=200, n_td=100, n_th=3, n_s=100, embedding_type="mix")
         run_pairs("cfg3 geometry at d=256 F=1024 H=8 f16x3: al_mix dx=2 B=512 T=50, split mask (data)", build(2, 256, 1024, 8, 3, "mix", "f16x3"),
                   batch, 50, args.steps, args.pairs, geo)
+    if "1w" in want:
+        batch = HiddenLocation(n_query_init=200, device=dev).sample_batch(1000)
+        geo = dict(dx=2, dy=1, d=128, F=512, H=4, L=3, C=10, n_c0=1, n_q0=200, n_td=0, n_th=2, n_s=2)
+        run_pairs("headline geometry at d=128 F=512 H=4 f16x3: location_finding B=1000 T=30", build(2, 128, 512, 4, 2, "theta", "f16x3"),
+                  batch, 30, args.steps, args.pairs, geo, key="x1")
     if "5" in want:
         task = PsychometricTask(n_query_init=200, n_context_init=1, device=dev)
         batch = task.sample_batch(256)
