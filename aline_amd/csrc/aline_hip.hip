@@ -14,6 +14,7 @@
 #include "attn3.h"
 #include "backward.h"
 #include "attn_bwd_wide.h"
+#include "attn_bwd_long.h"
 #include "attn_bwd8.h"
 #include "tail_bwd.h"
 #include "attn_bwd_mfma.h"
@@ -1606,6 +1607,19 @@ static int launch_attention_bwd_wide(const BCtx &c, const float *qkv, const floa
   return ALINE_OK;
 }
 
+// head_dim 32, 49 - 160 keys on the f16 matrix pipe, a head's key tiles split over G waves (attn_bwd_long.h).  Its LDS holds the key list
+// and 8 bytes per padded token row beside the fixed blocks (92 KB at most, <3, 2>): N <= 8736 rows in every shape, beyond its limit a shape is refused
+template <int TPW, int G>
+static int launch_attention_bwd_long(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, unsigned *mw,
+                                     const unsigned *da_scale) {
+  const size_t smem = abwl::lds_bytes(TPW, G, c.g.N);
+  if (smem > 160 * 1024) return ALINE_EUNSUPPORTED;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&abwl::attention_bwd_long_kernel<TPW, G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL((abwl::attention_bwd_long_kernel<TPW, G>), dim3((unsigned)c.g.B), dim3(64 * abwl::WAVES), smem, c.st, c.g, c.m->d, qkv, dA, aout, dqkv, mw, da_scale);
+  CHECK_LAUNCH();
+  return ALINE_OK;
+}
+
 template <int NKT>
 static int launch_attention_bwd8(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, const unsigned *da_scale) {
   const size_t smem = abw8::lds_bytes(NKT, c.g.N);
@@ -1647,6 +1661,19 @@ int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float
         if (nkt == 2) return launch_attention_bwd_wide<64, 2>(c, qkv, dA, aout, dqkv, mw, key_rows_only ? 1 : 0, wide_scale);
         return launch_attention_bwd_wide<64, 3>(c, qkv, dA, aout, dqkv, mw, key_rows_only ? 1 : 0, wide_scale);      // (cfg5: 1 + 29 context + 4 targets = 34 keys)
       }
+    }
+  }
+  if constexpr (HD == 32) {
+    // 4 - 10 key tiles of an F16X3 model, given the scale word of dA: the key tiles of a head over a group of waves (attn_bwd_long.h)
+    const int nkt = (max_keys + 15) / 16;
+    if (mfma_on && aout && da_scale && nkt >= 4 && nkt <= 10 && c.m->d % HD == 0 && bwd_grad_f16(*c.m)) {
+      if (key_rows_only) return ALINE_EUNSUPPORTED;      // (kv_sparse ends at 48 keys: the kernel writes whole rows)
+      unsigned *mw = out_max ? new_scale_word(c) : nullptr;
+      if (out_max) *out_max = mw;
+      if (nkt == 4) return launch_attention_bwd_long<2, 2>(c, qkv, dA, aout, dqkv, mw, da_scale);
+      if (nkt <= 6) return launch_attention_bwd_long<3, 2>(c, qkv, dA, aout, dqkv, mw, da_scale);
+      if (nkt <= 8) return launch_attention_bwd_long<2, 4>(c, qkv, dA, aout, dqkv, mw, da_scale);
+      return launch_attention_bwd_long<3, 4>(c, qkv, dA, aout, dqkv, mw, da_scale);
     }
   }
   if (mfma_on && HD == abwd::HD && c.m->d == abwd::D && max_keys <= abwd::MAXK) {
