@@ -1386,7 +1386,9 @@ static bool fused_attn_block(const aline_model &m, int max_keys) {
   return m.d == abwd::D && m.H == abwd::H && max_keys <= abwd::MAXK && !dbg(ALINE_DBG_NO_BWD_ATTN_BLOCK);
 }
 
-BwdPlan make_bwd_plan(const aline_model &m, int B, int P, int n_td, int tc) {
+static int bwd_max_keys(const aline_model &m, const aline_rollout &r) { return r.n_ctx0 + std::max((int)r.T, 1) - 1 + r.n_target_data + m.n_theta; }
+// max_keys: the key count of the backward's last (largest) chunk -- it sizes the key buffers of the image recompute (x3_host.h: recompute_plan)
+BwdPlan make_bwd_plan(const aline_model &m, int B, int P, int n_td, int tc, int max_keys) {
   BwdPlan p{};
   const bool ft = bwd_fused_tail(m);
   const size_t N = (size_t)P + n_td + m.n_theta, I = (size_t)B * tc, M = I * N, d = m.d, F = m.F, L = m.L;
@@ -1420,8 +1422,8 @@ BwdPlan make_bwd_plan(const aline_model &m, int B, int P, int n_td, int tc) {
   p.Kcnt = take(I * 2);
   p.Scale = take(16 * 16);      // (unsigned) ring of 16 max-|dY| words (one per 16-word line) of the scaled f16 gradient products
   p.rc_width = image_recompute_width(m);
-  if (p.rc_width == x3::D) p.rc3 = x3::recompute_plan(m, (long)I, (int)N, take);
-  else if (p.rc_width == x5::D) p.rc5 = x5::recompute_plan(m, (long)I, (int)N, take);
+  if (p.rc_width == x3::D) p.rc3 = x3::recompute_plan(m, (long)I, (int)N, max_keys, take);
+  else if (p.rc_width == x5::D) p.rc5 = x5::recompute_plan(m, (long)I, (int)N, max_keys, take);
   p.total = off;
   return p;
 }
@@ -1630,10 +1632,24 @@ static int launch_attention_bwd8(const BCtx &c, const float *qkv, const float *d
   return ALINE_OK;
 }
 
+// Which matrix-pipe attention backward serves head_dim hd at max_keys keys, given the attention output and (have_da_scale) the scale word
+// of dA: ABW_WIDE (attn_bwd_wide.h: <= 3 key tiles), ABW_LONG (attn_bwd_long.h: 4 - 10 key tiles at head_dim 32 of a model whose gradient
+// products run on the f16 pipe), or ABW_NONE.  Both kernels read K / V of the key rows only -- the forward recompute decides by this
+// whether Q may come from the layer kernel (backward_impl: rc_q).
+enum { ABW_NONE = 0, ABW_WIDE, ABW_LONG };
+static int attn_bwd_matrix_pipe(const aline_model &m, int hd, int max_keys, bool have_aout, bool have_da_scale) {
+  if (dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) || !have_aout || (hd != 32 && hd != 64) || m.d % hd != 0) return ABW_NONE;      // (the switch: the VALU kernel, A/B measurements)
+  const int nkt = (max_keys + 15) / 16;
+  if (nkt <= 3) return ABW_WIDE;      // (<32, 4> spills 64 registers: beyond 48 keys the kernels below)
+  if (hd == 32 && have_da_scale && nkt <= 10 && bwd_grad_f16(m)) return ABW_LONG;
+  return ABW_NONE;
+}
+
 template <int HD>
 int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float *dqkv, int max_keys, const float *aout = nullptr,
                          unsigned **out_max = nullptr, bool key_rows_only = false, const unsigned *da_scale = nullptr) {
   const bool mfma_on = !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA);      // 0: the VALU kernel (A/B measurements)
+  const int pipe = attn_bwd_matrix_pipe(*c.m, HD, max_keys, aout != nullptr, da_scale != nullptr);
   if (out_max) *out_max = nullptr;
   if constexpr (HD == 8) {
     // d = 32 / 4 heads beyond the fused attention block's 48 keys (cfg3): the f16 matrix pipe (attn_bwd8.h), given the scale word of dA
@@ -1646,7 +1662,7 @@ int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float
   }
   if constexpr (HD == 32 || HD == 64) {
     const int nkt = (max_keys + 15) / 16;
-    if (mfma_on && aout && nkt <= 3 && c.m->d % HD == 0) {      // (<32, 4> spills 64 registers: beyond 48 keys the VALU kernel)
+    if (pipe == ABW_WIDE) {
       unsigned *mw = (out_max && bwd_grad_f16(*c.m)) ? new_scale_word(c) : nullptr;
       if (out_max) *out_max = mw;
       const unsigned *wide_scale = (da_scale && bwd_grad_f16(*c.m)) ? da_scale : nullptr;      // F16X3 model + the scale word of dA: the f16 twin
@@ -1666,7 +1682,7 @@ int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float
   if constexpr (HD == 32) {
     // 4 - 10 key tiles of an F16X3 model, given the scale word of dA: the key tiles of a head over a group of waves (attn_bwd_long.h)
     const int nkt = (max_keys + 15) / 16;
-    if (mfma_on && aout && da_scale && nkt >= 4 && nkt <= 10 && c.m->d % HD == 0 && bwd_grad_f16(*c.m)) {
+    if (pipe == ABW_LONG) {
       if (key_rows_only) return ALINE_EUNSUPPORTED;      // (kv_sparse ends at 48 keys: the kernel writes whole rows)
       unsigned *mw = out_max ? new_scale_word(c) : nullptr;
       if (out_max) *out_max = mw;
@@ -1746,7 +1762,7 @@ int launch_tail(const BCtx &c, int l, const float *X, const float *A, float *Y, 
 extern "C" size_t aline_rollout_backward_workspace_bytes(const aline_model *m, const aline_rollout *r,
                                                          int t_chunk) {
   if (!m || !r || validate_model(*m, 0) != 0 || t_chunk < 1) return 0;
-  return make_bwd_plan(*m, r->B, r->P, r->n_target_data, std::min(t_chunk, (int)r->T)).total * sizeof(float);
+  return make_bwd_plan(*m, r->B, r->P, r->n_target_data, std::min(t_chunk, (int)r->T), bwd_max_keys(*m, *r)).total * sizeof(float);
 }
 
 extern "C" int aline_rollout_backward(const aline_model *m, const aline_rollout *r, const float *g_logp,
@@ -1798,6 +1814,43 @@ static int launch_attn_block_bwd(hipStream_t st, const abwd::BlockArgs &ba, int 
 
 struct StageIO { int stages; const float *x_in, *z_in, *d_in; float *d_out; };
 
+// How the forward of the chunk of steps [tA, tA + nt_steps) of a backward is recomputed: evaluated by the chunk loop of backward_impl, and
+// reported by aline_backward_recompute_name.
+struct ChunkFwd {
+  int max_keys;        // most keys an instance of the chunk shows
+  bool use_saved;      // nothing is recomputed: the rows the s3 rollout saved (aline_rollout.saved_acts)
+  bool ckv;            // fused attention block (d = 32): Q of every row, compact K / V of the key rows
+  bool rc_now;         // the rollout's own layer kernel over the instances (x3_host.h: recompute), everything but QKV
+  bool rc_q;           // ... and Q; K | V of the key rows from key_list_kernel + the row-gather GEMM
+  bool kv_sparse;      // the in-projection's gradient products over the key rows only
+};
+static bool image_recompute_stages(const aline_model &m, int stages) {
+  return (stages & ST_EMBED) && (stages & ST_ENC) && !bwd_fused_tail(m);
+}
+static ChunkFwd chunk_fwd(const aline_model &m, const aline_rollout &r, int stages, int tA, int nt_steps) {
+  const bool do_emb = stages & ST_EMBED, do_enc = stages & ST_ENC, do_head = stages & ST_HEAD;
+  const int n_t = r.n_target_data + m.n_theta, N = r.P + n_t, d = m.d, hd = m.H > 0 ? d / m.H : 0;
+  ChunkFwd f{};
+  f.max_keys = r.n_ctx0 + tA + nt_steps - 1 + n_t;
+  const int max_keys = f.max_keys;
+  f.use_saved = r.saved_acts && do_emb && do_enc && do_head && saved_acts_usable(m, r) && !dbg(ALINE_DBG_NO_BWD_SAVED_ACTS);
+  // With the fused attention-block backward nothing downstream reads QKV: Q for every row, K / V for the key rows only
+  // (key_list_kernel + row-gather GEMM, as the generic rollout pipeline does), one buffer for all layers.
+  f.ckv = do_enc && fused_attn_block(m, max_keys) && hd == abwd::HD && max_keys < N;
+  // d = 256: up to 160 keys (beyond 64 on the long-key layout of the chunk), d = 512: up to 64
+  const int rc_width = image_recompute_width(m);
+  f.rc_now = rc_width && image_recompute_stages(m, stages) && !f.use_saved && !f.ckv && max_keys <= (rc_width == x3::D ? x3::NK_MAX : x5::NK_MAX);
+  // ... Q too when a matrix-pipe attention backward will run for the chunk (it reads K / V of the key rows only: those come from a row-gather
+  // GEMM on the key list, 16 % of the rows at the d = 256 headline shape, scattered into the [M, 3 d] buffer the kernel indexes by token row).
+  // (the per-op backward hands the attention backward the attention output always, and the scale word of dA iff bwd_grad_f16)
+  f.rc_q = f.rc_now && max_keys < N && attn_bwd_matrix_pipe(m, hd, max_keys, true, bwd_grad_f16(m)) != ABW_NONE;
+  // The same key list on the way back: dK / dV are zero outside the key rows, so the in-projection's gradient products split into a
+  // dense Q part (a third of the columns) and a K | V part over the key rows only (gathered by the list; dX scattered back)
+  f.kv_sparse = do_enc && !f.ckv && bwd_grad_f16(m) && !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) && !dbg(ALINE_DBG_NO_BWD_KV_SPARSE) &&
+                (hd == 32 || hd == 64) && max_keys <= 48 && max_keys < N && d % 256 == 0;
+  return f;
+}
+
 static int backward_impl(const aline_model *m, const aline_rollout *r, const float *g_logp, const float *g_ll,
                          const float *g_pm, const float *g_ps, const float *g_pw, const aline_grads *gr, int t_chunk,
                          void *ws, size_t ws_bytes, void *stream, StageIO io) {
@@ -1815,7 +1868,7 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
   const int tc = std::min(t_chunk, (int)r->T);
   BCtx c;
   c.m = m;
-  c.pl = make_bwd_plan(*m, r->B, r->P, r->n_target_data, tc);
+  c.pl = make_bwd_plan(*m, r->B, r->P, r->n_target_data, tc, bwd_max_keys(*m, *r));
   if (ws_bytes < c.pl.total * sizeof(float)) return ALINE_EWORKSPACE;
   c.ws = static_cast<float *>(ws);
   c.st = static_cast<hipStream_t>(stream);
@@ -1842,7 +1895,7 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
   (void)hipMemsetAsync(c.at(c.pl.dEy), 0, (size_t)rows_y * d * sizeof(float), c.st);
   }
 
-  const bool img_rc = c.pl.rc_width && do_emb && do_enc && !ft;
+  const bool img_rc = c.pl.rc_width && image_recompute_stages(*m, io.stages);
   if (img_rc) {
     if (c.pl.rc_width == x3::D) TRY(x3::pack_weights(*m, reinterpret_cast<unsigned *>(c.at(c.pl.rc3.img)), nullptr, c.st));
     else TRY(x5::pack_weights(*m, reinterpret_cast<unsigned *>(c.at(c.pl.rc5.img)), nullptr, c.st));
@@ -1854,9 +1907,10 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
     Geo &g = c.g;
     g.B = I; g.P = P; g.n_td = n_td; g.n_th = n_th; g.N = N; g.n_ctx = 0; g.role = r->role;
     g.tmask = r->target_mask; g.inst_B = B; g.inst_t0 = tA; g.n_ctx0 = r->n_ctx0;
-    const int max_keys = r->n_ctx0 + tA + nt_steps - 1 + n_t;
+    const ChunkFwd cf = chunk_fwd(*m, *r, io.stages, tA, nt_steps);
+    const int max_keys = cf.max_keys;
     // layer inputs / attention outputs of this chunk: recomputed into the workspace, or the rows the s3 rollout saved (aline_rollout.saved_acts)
-    const bool use_saved = r->saved_acts && do_emb && do_enc && do_head && saved_acts_usable(*m, *r) && !dbg(ALINE_DBG_NO_BWD_SAVED_ACTS);
+    const bool use_saved = cf.use_saved;
     const size_t sv_rows = (size_t)r->T * B * N, sv_off = (size_t)tA * B * N * d;
     auto Xs = [&](int l) { return use_saved ? r->saved_acts + (size_t)l * sv_rows * d + sv_off : c.at(c.pl.Xs) + (size_t)l * M * d; };
     auto QKVl = [&](int l) { return c.at(c.pl.QKV) + (size_t)l * M * 3 * d; };
@@ -1881,7 +1935,7 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
     }
     // With the fused attention-block backward nothing downstream reads QKV: Q for every row, K / V for the key rows only
     // (key_list_kernel + row-gather GEMM, as the generic rollout pipeline does), one buffer for all layers.
-    const bool ckv = do_enc && fused_attn_block(*m, max_keys) && hd == abwd::HD && max_keys < N;
+    const bool ckv = cf.ckv;
     int *keyidx = reinterpret_cast<int *>(c.at(c.pl.KeyIdx)), *kcnt = reinterpret_cast<int *>(c.at(c.pl.Kcnt));
     // compact K / V of layer l [I * max_keys, 2 d] (kept for the backward), then dK | dV of the layer in flight, then Q
     const size_t kv_floats = (size_t)I * max_keys * 2 * d;
@@ -1891,15 +1945,9 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
       hipLaunchKernelGGL(key_list_kernel, dim3(I), dim3(256), 0, c.st, g, max_keys, keyidx, kcnt);
       CHECK_LAUNCH();
     }
-    // (d = 256 / 512, <= 64 keys: everything but QKV from the rollout's layer kernel run over the instances)
-    const bool rc_now = img_rc && !use_saved && !ckv && max_keys <= x3::WNK;
-    // ... Q too when the matrix-pipe attention backward runs (it reads K / V of the key rows only: those come from a row-gather GEMM on
-    // the key list, 16 % of the rows at the d = 256 headline shape, scattered into the [M, 3 d] buffer the kernel indexes by token row)
-    const bool rc_q = rc_now && max_keys < N && max_keys <= 48 && (hd == 32 || hd == 64) && !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA);
-    // The same key list on the way back: dK / dV are zero outside the key rows, so the in-projection's gradient products split into a
-    // dense Q part (a third of the columns) and a K | V part over the key rows only (gathered by the list; dX scattered back)
-    const bool kv_sparse = do_enc && !ckv && bwd_grad_f16(*m) && !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) && !dbg(ALINE_DBG_NO_BWD_KV_SPARSE) &&
-                           (hd == 32 || hd == 64) && max_keys <= 48 && max_keys < N && d % 256 == 0;
+    // (chunk_fwd: everything but QKV from the rollout's layer kernel run over the instances; Q too when a matrix-pipe attention backward
+    //  follows -- K | V of the key rows then come from a row-gather GEMM on the key list --; the in-projection's gradient products over key rows only)
+    const bool rc_now = cf.rc_now, rc_q = cf.rc_q, kv_sparse = cf.kv_sparse;
     if (rc_q || kv_sparse) {
       hipLaunchKernelGGL(key_list_kernel, dim3(I), dim3(256), 0, c.st, g, max_keys, keyidx, kcnt);
       CHECK_LAUNCH();
@@ -2260,6 +2308,16 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
     CHECK_LAUNCH();
   }
   return ALINE_OK;
+}
+
+extern "C" int aline_backward_recompute_name(const aline_model *m, const aline_rollout *r, int t0, int nt, char *buf, size_t n) {
+  if (!m || !r || !buf || n == 0 || t0 < 0 || nt < 1 || t0 + nt > r->T) return ALINE_EINVAL;
+  TRY(validate_model(*m, 0));
+  const ChunkFwd cf = chunk_fwd(*m, *r, ST_ALL, t0, nt);
+  if (cf.use_saved) snprintf(buf, n, "saved activations");
+  else if (cf.rc_now) snprintf(buf, n, "%s", image_recompute_width(*m) == x3::D ? x3::recompute_kernel_name(cf.max_keys) : x5::recompute_kernel_name(cf.max_keys));
+  else snprintf(buf, n, "generic");
+  return cf.rc_q ? 1 : 0;
 }
 
 extern "C" int aline_rollout_backward_ex(const aline_model *m, const aline_rollout *r, const float *g_logp,

@@ -41,61 +41,107 @@ static int pack_weights(const aline_model &mm, unsigned *img, unsigned *range_fl
 // attention kernel and two LayerNorm kernels per layer: 15 % of the d = 256 step); this runs the rollout's own layer kernel over
 // the instances instead (layer_save_kernel: the same arithmetic, plus fp32 stores of those rows).  The buffers are float offsets
 // into the backward workspace.
-struct RecomputePlan { size_t img, in, a, b, kv, keys, kcnt, kx, kpos; };
+struct RecomputePlan { size_t img, in, a, b, kv, keys, kcnt, kx, kpos; int groups; };      // groups: blocks of the KV_EP layout per instance the key buffers hold
 static bool recompute_model_ok(const aline_model &m) {
   return m.precision == ALINE_PREC_F16X3 && m.d == D && m.H == H && m.F % 32 == 0 &&
          (size_t)NBUF * CHUNK_BYTES + (size_t)layer_params(m.F) * 4 <= 160 * 1024;
 }
+// max_keys: the largest key count of a chunk of the backward.  The key list, the key image and the K / V buffer hold the blocks of the
+// largest chunk that can take this recompute: key_groups of min(max_keys, NK_MAX) -- a backward that goes beyond NK_MAX still has earlier
+// chunks within it, on up to NK_MAX / WNK blocks (a backward within WNK keys, and every width without the long layout, is sized as before)
 template <class Take>
-static RecomputePlan recompute_plan(const aline_model &m, long I, int N, Take take) {
+static RecomputePlan recompute_plan(const aline_model &m, long I, int N, int max_keys, Take take) {
   RecomputePlan p{};
-  const long tpe = (N + 15) / 16;
+  const long tpe = (N + 15) / 16, kg = p.groups = key_groups(std::min(max_keys, NK_MAX));
   const size_t im = (size_t)img_pieces(I * tpe) * 4;
   p.img = take((size_t)image_words(m.L, m.F, m.C));
   p.in = take(im); p.a = take(im); p.b = take(im);
-  p.kv = take((size_t)I * KV_EP * 4);
-  p.keys = take((size_t)I * WNK); p.kcnt = take((size_t)I * 2);
-  p.kx = take((size_t)img_pieces(I * (WNK / 16)) * 4);
+  p.kv = take((size_t)I * kg * KV_EP * 4);
+  p.keys = take((size_t)I * kg * WNK); p.kcnt = take((size_t)I * 2);
+  p.kx = take((size_t)img_pieces(I * kg * (WNK / 16)) * 4);
   p.kpos = take((size_t)I * tpe * 16 / 2 + 1);
   return p;
 }
 struct RecomputeRows { float *Q[ALINE_MAX_LAYERS]; long q_ld; float *A[ALINE_MAX_LAYERS], *U1[ALINE_MAX_LAYERS], *X1[ALINE_MAX_LAYERS], *Hid[ALINE_MAX_LAYERS], *U2[ALINE_MAX_LAYERS], *Y[ALINE_MAX_LAYERS]; };
-// g: the instance geometry of the chunk (Geo.inst_B > 0); max_keys <= WNK
+// the layer kernel that recomputes a chunk whose instances show up to max_keys keys (the backward's query reports it)
+static bool recompute_long(int max_keys) { return key_groups(max_keys) > 1; }
+#define X3_STR2(x) #x
+#define X3_STR(x) X3_STR2(x)
+static const char *recompute_kernel_name(int max_keys) {
+  return recompute_long(max_keys) ? X3_STR(X3_NS) "::layer_save_long_kernel" : X3_STR(X3_NS) "::layer_save_kernel";
+}
+#undef X3_STR
+#undef X3_STR2
+// g: the instance geometry of the chunk (Geo.inst_B > 0); max_keys <= NK_MAX, the chunk's own.  A chunk beyond WNK keys runs on the long-key
+// layout of its key_groups(max_keys) blocks, every other chunk on the one-block layout; a chunk that needs more blocks than the plan holds is refused
 static int recompute(const aline_model *m, const Geo &g, int max_keys, const float *Ex, const float *Ey, int ey_rows, float *ws, const RecomputePlan &pl,
                      const RecomputeRows &rows, hipStream_t st) {
   const int I = g.B, N = g.N, F = m->F, tpe = (N + 15) / 16;
   const long tiles = (long)I * tpe;
+  if (max_keys > NK_MAX || key_groups(max_keys) > pl.groups) return ALINE_EUNSUPPORTED;
   unsigned *img = reinterpret_cast<unsigned *>(ws + pl.img);
   u32x4 *XIN = reinterpret_cast<u32x4 *>(ws + pl.in), *XA = reinterpret_cast<u32x4 *>(ws + pl.a), *XB = reinterpret_cast<u32x4 *>(ws + pl.b);
   u32x4 *KV = reinterpret_cast<u32x4 *>(ws + pl.kv), *KX = reinterpret_cast<u32x4 *>(ws + pl.kx);
   int *keyrow = reinterpret_cast<int *>(ws + pl.keys), *kcnt = reinterpret_cast<int *>(ws + pl.kcnt);
   short *keypos = reinterpret_cast<short *>(ws + pl.kpos);
+  const bool lk = recompute_long(max_keys);
+  const int ktiles = 4 * key_groups(max_keys);
   AsmArgs aa{};
   aa.g = g; aa.tpe = tpe; aa.Ex = Ex; aa.Ey = Ey; aa.ey_rows = ey_rows; aa.theta_tokens = m->theta_tokens; aa.X = XIN; aa.range_flag = nullptr;
   hipLaunchKernelGGL(assemble_kernel, grid1d((size_t)tiles * NKS * 64), dim3(256), 0, st, aa);
   CHECK_LAUNCH();
+#if X3_LONGKEYS
+  if (lk) hipLaunchKernelGGL(keys_long_kernel, dim3(I), dim3(256), 0, st, g, tpe, keyrow, kcnt, keypos, XIN, KX, ktiles);
+  else
+#endif
   hipLaunchKernelGGL(keys_kernel, dim3(I), dim3(256), 0, st, g, tpe, keyrow, kcnt, keypos, XIN, KX);
   CHECK_LAUNCH();
   const long lw = layer_words(F);
   const size_t smem_layer = (size_t)NBUF * CHUNK_BYTES + (size_t)layer_params(F) * 4;
   const size_t smem_kv = (size_t)NBUF * CHUNK_BYTES + 2 * D * 4;
+  const int cus = device_cus();
+  // (the chunk's largest key count bounds every instance's: every key tile an attention variant can read in the chunk is written in it)
+  const int nkt2 = 2 * ((std::min(max_keys, 16 * ktiles) + 31) / 32);
+  const int kv_groups = (int)(((long)I * nkt2 + WAVES - 1) / WAVES);
+#if X3_LONGKEYS
+  // long layout: the rollout's split rule (groups of key tiles that do not fill the chip: one job -- K | V x channel half -- per workgroup)
+  constexpr int NJ = 2 * CPK;
+  const bool split = lk && (kv_groups * NJ + cus - 1) / cus < NJ * ((kv_groups + cus - 1) / cus);
+  const dim3 kv_grid(split ? (unsigned)(std::min(kv_groups, std::max(1, cus / NJ)) * NJ) : (unsigned)std::min(kv_groups, cus));
+  if (lk) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_save_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_layer);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_all_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_split_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
+  }
+#else
+  const dim3 kv_grid((unsigned)std::min(kv_groups, cus));
+  if (lk) return ALINE_EUNSUPPORTED;
+#endif
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_save_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_layer);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kv_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_kv);
-  const int cus = device_cus();
-  const int nkt2 = 2 * ((std::min(max_keys, WNK) + 31) / 32);
   const u32x4 *xin = XIN;
   for (int l = 0; l < m->L; ++l) {
     u32x4 *xout = (l & 1) ? XB : XA;
     KvArgs ka{};
     ka.g = g; ka.tpe = tpe; ka.nkt2 = nkt2; ka.X = KX; ka.img = img + l * lw; ka.F = F; ka.keyrow = keyrow; ka.kcnt = kcnt; ka.KV = KV;
-    ka.ngroups = (int)(((long)I * nkt2 + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(kv_all_kernel, dim3((unsigned)std::min(ka.ngroups, cus)), dim3(THREADS), smem_kv, st, ka);
+    ka.ngroups = kv_groups;
+#if X3_LONGKEYS
+    if (lk && split) hipLaunchKernelGGL(kv_split_long_kernel, kv_grid, dim3(THREADS), smem_kv, st, ka, ktiles);
+    else if (lk) hipLaunchKernelGGL(kv_all_long_kernel, kv_grid, dim3(THREADS), smem_kv, st, ka, ktiles);
+    else
+#endif
+    hipLaunchKernelGGL(kv_all_kernel, kv_grid, dim3(THREADS), smem_kv, st, ka);
     CHECK_LAUNCH();
     LayerArgs la{};
     la.g = g; la.tpe = tpe; la.ngroups = (int)((tiles + WAVES - 1) / WAVES);
     la.XIN = xin; la.XOUT = xout; la.img = img + l * lw; la.F = F; la.KV = KV; la.kcnt = kcnt; la.range_flag = nullptr; la.keypos = keypos; la.KXout = KX;
     la.svQ = rows.Q[l]; la.svQ_ld = rows.q_ld; la.svA = rows.A[l]; la.svU1 = rows.U1[l]; la.svX1 = rows.X1[l]; la.svHid = rows.Hid[l]; la.svU2 = rows.U2[l]; la.svY = rows.Y[l];
-    hipLaunchKernelGGL(layer_save_kernel, dim3((unsigned)std::min(la.ngroups, cus)), dim3(THREADS), smem_layer, st, la);
+    const dim3 layer_grid((unsigned)std::min(la.ngroups, cus));
+#if X3_LONGKEYS
+    if (lk) hipLaunchKernelGGL(layer_save_long_kernel, layer_grid, dim3(THREADS), smem_layer, st, la, ktiles);
+    else
+#endif
+    hipLaunchKernelGGL(layer_save_kernel, layer_grid, dim3(THREADS), smem_layer, st, la);
     CHECK_LAUNCH();
     xin = xout;
   }

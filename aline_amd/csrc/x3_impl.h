@@ -1110,6 +1110,8 @@ __global__ __launch_bounds__(THREADS) void layer_save_kernel(LayerArgs a) { laye
 // the layer on the long-key layout: a rollout that shows an episode 65 .. NK_MAX keys (every step of it, also those with few keys)
 template <bool LAST>
 __global__ __launch_bounds__(THREADS) X3_NO_PK_F32 void layer_long_kernel(LayerArgs a, int ktiles) { layer_body<LAST, false, true>(a, ktiles); }
+// ... with the fp32 side outputs of layer_save_kernel: the forward recompute of a backward chunk that shows an instance 65 .. NK_MAX keys
+__global__ __launch_bounds__(THREADS) X3_NO_PK_F32 void layer_save_long_kernel(LayerArgs a, int ktiles) { layer_body<false, true, true>(a, ktiles); }
 #endif
 #endif
 

@@ -195,6 +195,10 @@ size_t aline_rollout_saved_acts_bytes(const aline_model *m, const aline_rollout 
 /* Name (as rocprofv3 prints it, template arguments included) of the dominant kernel of that path for (m, r) -- the launch
  * the ev_kernel_start / ev_kernel_stop pair brackets -- written to buf; returns the ALINE_PATH_* value or a negative code. */
 int aline_rollout_kernel_name(const aline_model *m, const aline_rollout *r, char *buf, size_t n);
+/* the kernel that recomputes the forward for the chunk of steps [t0, t0 + nt) of a training backward:
+ * "x3::layer_save_long_kernel", "x3::layer_save_kernel", "x5::layer_save_kernel", "saved activations" (s3 SAVE rollout) or "generic";
+ * returns 1 if Q comes from that kernel too (rc_q), else 0; negative on error.  Host logic only. */
+int aline_backward_recompute_name(const aline_model *m, const aline_rollout *r, int t0, int nt, char *buf, size_t n);
 /* Task.update_batch equivalent for callers that want the reference layout back
  * (tasks/base_task.py:133-154): context_x/y [B,n_ctx0+T,*] in order of entry, query remainder. */
 int aline_rollout_export(const aline_rollout *r, int n_ctx, float *context_x, float *context_y,
