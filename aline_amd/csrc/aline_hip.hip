@@ -1362,14 +1362,16 @@ namespace {
 struct BwdPlan {
   size_t Xs, QKV, A, U1, X1, Hid, U2, HidA, HidG, dXa, dXb, dQKV, dHid, dTmp, Ex, Ey, EHx, EHy, dEx, dEy, Wt, KeyIdx, Kcnt, Tvec, Scale,
       total;
-  int rc_width;                                   // 0, or the width (256 / 512) whose tile-image layer kernel recomputes the forward (x3_host.h: recompute)
-  x3::RecomputePlan rc3; x5::RecomputePlan rc5;
+  int rc_width;                                   // 0, or the width (128 / 256 / 512) whose tile-image layer kernel recomputes the forward (x3_host.h: recompute)
+  x3::RecomputePlan rc3; x5::RecomputePlan rc5; x1::RecomputePlan rc1;
 };
 // Forward recompute of the per-op backward on the rollout's own layer kernel (x3_host.h).  ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE: the generic kernels.
 static int image_recompute_width(const aline_model &m) {
   if (dbg(ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE) || dbg(ALINE_DBG_BWD_RECOMPUTE_F32)) return 0;
-  return x3::recompute_model_ok(m) ? x3::D : x5::recompute_model_ok(m) ? x5::D : 0;
+  return x3::recompute_model_ok(m) ? x3::D : x5::recompute_model_ok(m) ? x5::D : x1::recompute_model_ok(m) ? x1::D : 0;
 }
+// most keys of a chunk that width's layer kernel serves
+static int image_recompute_max_keys(int rc_width) { return rc_width == x3::D ? x3::NK_MAX : rc_width == x5::D ? x5::NK_MAX : x1::NK_MAX; }
 
 // Fused token-local tail (tail_bwd.h) for the small-width model: U1 / X1 / Hid / U2 are never stored.  ALINE_BWD_TAIL=0
 // switches back to the per-op pipeline (A/B measurements).
@@ -1424,6 +1426,7 @@ BwdPlan make_bwd_plan(const aline_model &m, int B, int P, int n_td, int tc, int 
   p.rc_width = image_recompute_width(m);
   if (p.rc_width == x3::D) p.rc3 = x3::recompute_plan(m, (long)I, (int)N, max_keys, take);
   else if (p.rc_width == x5::D) p.rc5 = x5::recompute_plan(m, (long)I, (int)N, max_keys, take);
+  else if (p.rc_width == x1::D) p.rc1 = x1::recompute_plan(m, (long)I, (int)N, max_keys, take);
   p.total = off;
   return p;
 }
@@ -1837,9 +1840,9 @@ static ChunkFwd chunk_fwd(const aline_model &m, const aline_rollout &r, int stag
   // With the fused attention-block backward nothing downstream reads QKV: Q for every row, K / V for the key rows only
   // (key_list_kernel + row-gather GEMM, as the generic rollout pipeline does), one buffer for all layers.
   f.ckv = do_enc && fused_attn_block(m, max_keys) && hd == abwd::HD && max_keys < N;
-  // d = 256: up to 160 keys (beyond 64 on the long-key layout of the chunk), d = 512: up to 64
+  // d = 256: up to 160 keys (beyond 64 on the long-key layout of the chunk), d = 128 / 512: up to 64
   const int rc_width = image_recompute_width(m);
-  f.rc_now = rc_width && image_recompute_stages(m, stages) && !f.use_saved && !f.ckv && max_keys <= (rc_width == x3::D ? x3::NK_MAX : x5::NK_MAX);
+  f.rc_now = rc_width && image_recompute_stages(m, stages) && !f.use_saved && !f.ckv && max_keys <= image_recompute_max_keys(rc_width);
   // ... Q too when a matrix-pipe attention backward will run for the chunk (it reads K / V of the key rows only: those come from a row-gather
   // GEMM on the key list, 16 % of the rows at the d = 256 headline shape, scattered into the [M, 3 d] buffer the kernel indexes by token row).
   // (the per-op backward hands the attention backward the attention output always, and the scale word of dA iff bwd_grad_f16)
@@ -1898,6 +1901,7 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
   const bool img_rc = c.pl.rc_width && image_recompute_stages(*m, io.stages);
   if (img_rc) {
     if (c.pl.rc_width == x3::D) TRY(x3::pack_weights(*m, reinterpret_cast<unsigned *>(c.at(c.pl.rc3.img)), nullptr, c.st));
+    else if (c.pl.rc_width == x1::D) TRY(x1::pack_weights(*m, reinterpret_cast<unsigned *>(c.at(c.pl.rc1.img)), nullptr, c.st));
     else TRY(x5::pack_weights(*m, reinterpret_cast<unsigned *>(c.at(c.pl.rc5.img)), nullptr, c.st));
   }
   for (int tA = 0; tA < r->T; tA += tc) {
@@ -1958,6 +1962,11 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
         rr.q_ld = 3 * d;
         for (int l = 0; l < L; ++l) { rr.Q[l] = rc_q ? QKVl(l) : c.at(c.pl.dQKV); rr.A[l] = Al(l); rr.U1[l] = U1l(l); rr.X1[l] = X1l(l); rr.Hid[l] = Hidl(l); rr.U2[l] = U2l(l); rr.Y[l] = Xs(l + 1); }
         TRY(x3::recompute(m, g, max_keys, Ex, Ey, P, c.ws, c.pl.rc3, rr, c.st));
+      } else if (c.pl.rc_width == x1::D) {
+        x1::RecomputeRows rr{};
+        rr.q_ld = 3 * d;
+        for (int l = 0; l < L; ++l) { rr.Q[l] = rc_q ? QKVl(l) : c.at(c.pl.dQKV); rr.A[l] = Al(l); rr.U1[l] = U1l(l); rr.X1[l] = X1l(l); rr.Hid[l] = Hidl(l); rr.U2[l] = U2l(l); rr.Y[l] = Xs(l + 1); }
+        TRY(x1::recompute(m, g, max_keys, Ex, Ey, P, c.ws, c.pl.rc1, rr, c.st));
       } else {
         x5::RecomputeRows rr{};
         rr.q_ld = 3 * d;
@@ -2315,7 +2324,10 @@ extern "C" int aline_backward_recompute_name(const aline_model *m, const aline_r
   TRY(validate_model(*m, 0));
   const ChunkFwd cf = chunk_fwd(*m, *r, ST_ALL, t0, nt);
   if (cf.use_saved) snprintf(buf, n, "saved activations");
-  else if (cf.rc_now) snprintf(buf, n, "%s", image_recompute_width(*m) == x3::D ? x3::recompute_kernel_name(cf.max_keys) : x5::recompute_kernel_name(cf.max_keys));
+  else if (cf.rc_now) {
+    const int w = image_recompute_width(*m);
+    snprintf(buf, n, "%s", w == x3::D ? x3::recompute_kernel_name(cf.max_keys) : w == x5::D ? x5::recompute_kernel_name(cf.max_keys) : x1::recompute_kernel_name(cf.max_keys));
+  }
   else snprintf(buf, n, "generic");
   return cf.rc_q ? 1 : 0;
 }

@@ -34,13 +34,13 @@ static int pack_weights(const aline_model &mm, unsigned *img, unsigned *range_fl
   return ALINE_OK;
 }
 
-#if !X3_PAIRED
 // ---- forward recompute of the training backward (round 4) -----------------------------------------------------------------
-// The per-op backward of a d = 256 / 512 model needs, per layer, the attention output, both LayerNorm inputs and outputs and the
+// The per-op backward of a d = 128 / 256 / 512 model needs, per layer, the attention output, both LayerNorm inputs and outputs and the
 // hidden units of every (step, episode) INSTANCE of a chunk.  It used to recompute them with the generic kernels (four GEMMs, the
 // attention kernel and two LayerNorm kernels per layer: 15 % of the d = 256 step); this runs the rollout's own layer kernel over
 // the instances instead (layer_save_kernel: the same arithmetic, plus fp32 stores of those rows).  The buffers are float offsets
-// into the backward workspace.
+// into the backward workspace.  (x1, d = 128: the units of its layer kernel are tile PAIRS of an instance, its K / V kernel is
+// kv_all_kernel alone and its key buffers are one block.)
 struct RecomputePlan { size_t img, in, a, b, kv, keys, kcnt, kx, kpos; int groups; };      // groups: blocks of the KV_EP layout per instance the key buffers hold
 static bool recompute_model_ok(const aline_model &m) {
   return m.precision == ALINE_PREC_F16X3 && m.d == D && m.H == H && m.F % 32 == 0 &&
@@ -133,7 +133,7 @@ static int recompute(const aline_model *m, const Geo &g, int max_keys, const flo
     hipLaunchKernelGGL(kv_all_kernel, kv_grid, dim3(THREADS), smem_kv, st, ka);
     CHECK_LAUNCH();
     LayerArgs la{};
-    la.g = g; la.tpe = tpe; la.ngroups = (int)((tiles + WAVES - 1) / WAVES);
+    la.g = g; la.tpe = tpe; la.ngroups = (int)((layer_units(I, tpe) + WAVES - 1) / WAVES);
     la.XIN = xin; la.XOUT = xout; la.img = img + l * lw; la.F = F; la.KV = KV; la.kcnt = kcnt; la.range_flag = nullptr; la.keypos = keypos; la.KXout = KX;
     la.svQ = rows.Q[l]; la.svQ_ld = rows.q_ld; la.svA = rows.A[l]; la.svU1 = rows.U1[l]; la.svX1 = rows.X1[l]; la.svHid = rows.Hid[l]; la.svU2 = rows.U2[l]; la.svY = rows.Y[l];
     const dim3 layer_grid((unsigned)std::min(la.ngroups, cus));
@@ -147,7 +147,6 @@ static int recompute(const aline_model *m, const Geo &g, int max_keys, const flo
   }
   return ALINE_OK;
 }
-#endif
 
 // Eligibility of the tile-image path of this width (x3: d = 256 / 8 heads of 32, x5: d = 512 / 8 heads of 64) at reference
 // precision -- every product a 3-term f16 split on the matrix pipe.  Up to NK_MAX visible keys per episode: 64, or 160 where the

@@ -893,10 +893,10 @@ __device__ __forceinline__ void attention_long(f16x8 (&qh)[NKS], f16x8 (&ql)[NKS
 }
 #endif
 
-#if !X3_PAIRED
 // fp32 side outputs of layer_save_kernel: written once, read by other kernels much later -- streaming stores
 __device__ __forceinline__ void sv_store(float *p, const f32x4 &v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(p)); }
 
+#if !X3_PAIRED
 // (LONG: the long-key layout of `ktiles` = 4 groups key tiles per episode -- see KV_EP -- and attention against up to 10 key tiles)
 template <bool LAST, bool SAVE, bool LONG = false>
 __device__ __forceinline__ void layer_body(const LayerArgs &a, int ktiles_rt = 0) {

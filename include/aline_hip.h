@@ -196,7 +196,8 @@ size_t aline_rollout_saved_acts_bytes(const aline_model *m, const aline_rollout 
  * the ev_kernel_start / ev_kernel_stop pair brackets -- written to buf; returns the ALINE_PATH_* value or a negative code. */
 int aline_rollout_kernel_name(const aline_model *m, const aline_rollout *r, char *buf, size_t n);
 /* the kernel that recomputes the forward for the chunk of steps [t0, t0 + nt) of a training backward:
- * "x3::layer_save_long_kernel", "x3::layer_save_kernel", "x5::layer_save_kernel", "saved activations" (s3 SAVE rollout) or "generic";
+ * "x3::layer_save_long_kernel", "x3::layer_save_kernel", "x5::layer_save_kernel", "x1::layer_save_kernel", "saved activations" (s3 SAVE
+ * rollout) or "generic";
  * returns 1 if Q comes from that kernel too (rc_q), else 0; negative on error.  Host logic only. */
 int aline_backward_recompute_name(const aline_model *m, const aline_rollout *r, int t0, int nt, char *buf, size_t n);
 /* Task.update_batch equivalent for callers that want the reference layout back
@@ -322,7 +323,7 @@ enum { ALINE_DBG_DISABLE_FUSED = 1u << 0,      /* fused::rollout_f32_kernel off 
        ALINE_DBG_VALU_ATTENTION = 1u << 7,     /* generic pipeline: fp32 VALU attention instead of attn3 */
        ALINE_DBG_CES_GENERIC = 1u << 9,        /* CES likelihood: powf formulation */
        ALINE_DBG_FUSED_STAMPS = 1u << 10,      /* in-kernel phase stamps (diagnostic instantiations) */
-       ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE = 1u << 11,  /* per-op backward at d = 256 / 512: forward recompute on the generic kernels instead of x3 / x5 layer_save_kernel */
+       ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE = 1u << 11,  /* per-op backward at d = 128 / 256 / 512: forward recompute on the generic kernels instead of x1 / x3 / x5 layer_save_kernel */
        ALINE_DBG_NO_BWD_KV_SPARSE = 1u << 12,  /* per-op backward: the in-projection's gradient products over all rows x all 3 d columns (dK / dV of the non-key rows are zeros) */
        ALINE_DBG_SELECT_WORKGROUP = 1u << 13,  /* design selection: the workgroup-per-episode kernel also where one wave per episode would do */
        ALINE_DBG_S3_SELECT_KERNEL = 1u << 14,  /* s3 path: the design selection as a launch of its own (acq_select_wave_kernel) instead of inside the step kernel */

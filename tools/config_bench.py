@@ -7,6 +7,8 @@ mask T=30 nq=200 (F=128 literal config and F=2048).  cfg4 (CES EIG) is tools/eig
 pairs of the x3 path and the generic pipeline (ALINE_DISABLE_X3) in one process, one JSON line per pair.
 --configs 1w [--pairs N]: the headline geometry (location_finding B=1000 T=30 nq=200) at d=128/F=512/H=4 f16x3, the same pairs for the
 x1 path (ALINE_DISABLE_X1).
+--configs 1wt [--pairs N]: the training leg of 1w -- `train_step` at that geometry, N alternating pairs of the default backward
+(forward recompute on x1::layer_save_kernel) and ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE (the generic recompute); --pairs 0: the default alone.
 Random-init weights, synthetic task data, sampled designs, HIP-graph replay; which kernel path ran is reported."""
 import argparse
 import json
@@ -127,6 +129,48 @@ def run_pairs(name, model, batch, T, steps, pairs, geo, key="x3"):
                       "range": ro.range_status()}), flush=True)
 
 
+def timed_train_steps(model, batch, T, opt, steps):
+    from aline_amd.train import train_step
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        train_step(model, batch, T, optimizer=opt)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def run_train_pairs(name, model, batch, T, steps, pairs, flag="NO_BWD_IMAGE_RECOMPUTE"):
+    """Same-box alternating pairs: ms per `train_step` (sampled rollout, REINFORCE terms, backward, optimiser) with the library's default
+    backward and with the diagnostic switch `flag` set -- the generic forward recompute, which is what the library did for this shape before
+    the layer kernel's SAVE variant.  One JSON line per pair; which kernel recomputes the chunks is reported by the library.
+    (pairs = 0: timed steps of the default only -- the form a run on another build of the library takes, ALINE_HIP_LIB.)"""
+    import ctypes
+    from aline_amd import _lib
+    from aline_amd.train import train_step
+    opt = torch.optim.Adam(model.parameters(), lr=1e-5)
+    names = {}
+    for k, flags in (("default", []), ("generic_recompute", [flag])):
+        with _lib.debug(*flags):
+            for _ in range(2):                              # warm-up of both sides: code objects, graph cache, workspace
+                _, ro = train_step(model, batch, T, optimizer=opt)
+            buf = ctypes.create_string_buffer(64)      # (the answer for the last step's key count: the most any chunk of the backward shows)
+            rc = _lib.lib.aline_backward_recompute_name(ctypes.byref(ro.m), ctypes.byref(ro.r), T - 1, 1, buf, 64)
+            names[k] = [buf.value.decode(), rc]
+    if pairs == 0:
+        for i in range(3):
+            print(json.dumps({"config": name, "run": i, "lib": os.path.basename(_lib.LIB_PATH), "ms_per_train_step": round(timed_train_steps(model, batch, T, opt, steps), 2),
+                              "recompute": names["default"]}), flush=True)
+        return
+    for i in range(pairs):
+        ms = {}
+        for k, flags in (("default", []), ("generic_recompute", [flag])):
+            with _lib.debug(*flags):
+                ms[k] = timed_train_steps(model, batch, T, opt, steps)
+        print(json.dumps({"config": name, "pair": i, "B": int(ro.B), "T": T, "default_ms_per_train_step": round(ms["default"], 2),
+                          "generic_recompute_ms_per_train_step": round(ms["generic_recompute"], 2),
+                          "ratio": round(ms["generic_recompute"] / ms["default"], 4), "recompute": names}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="1,2,3,5")
@@ -181,6 +225,10 @@ def main():
         geo = dict(dx=2, dy=1, d=128, F=512, H=4, L=3, C=10, n_c0=1, n_q0=200, n_td=0, n_th=2, n_s=2)
         run_pairs("headline geometry at d=128 F=512 H=4 f16x3: location_finding B=1000 T=30", build(2, 128, 512, 4, 2, "theta", "f16x3"),
                   batch, 30, args.steps, args.pairs, geo, key="x1")
+    if "1wt" in want:
+        batch = HiddenLocation(n_query_init=200, device=dev).sample_batch(1000)
+        run_train_pairs("headline geometry at d=128 F=512 H=4 f16x3: location_finding B=1000 T=30, train_step",
+                        build(2, 128, 512, 4, 2, "theta", "f16x3"), batch, 30, args.steps, args.pairs)
     if "5" in want:
         task = PsychometricTask(n_query_init=200, n_context_init=1, device=dev)
         batch = task.sample_batch(256)
