@@ -97,6 +97,7 @@ def _load():
         "aline_rollout_saved_acts_bytes": (C.c_size_t, [MP, RP]),
         "aline_rollout_kernel_name": (C.c_int, [MP, RP, C.c_char_p, C.c_size_t]),
         "aline_backward_recompute_name": (C.c_int, [MP, RP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+        "aline_backward_dw_kernel_name": (C.c_int, [MP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
         "aline_rollout_export": (C.c_int, [RP, C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp]),
         "aline_compute_ll": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int, _fp, _fp]),
         "aline_eig_location_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_int,
@@ -136,7 +137,7 @@ def _load():
 lib, SIGNATURES = _load()
 
 # ---- diagnostics: the library never reads the environment; tests and A/B tools set its diagnostic word explicitly -------
-DBG = {"DISABLE_FUSED": 1 << 0, "DISABLE_X3": 1 << 2, "DISABLE_S3": 1 << 3,
+DBG = {"DISABLE_FUSED": 1 << 0, "NO_BWD_DW_NARROW": 1 << 1, "DISABLE_X3": 1 << 2, "DISABLE_S3": 1 << 3,
        "NO_LAYER_TAIL": 1 << 5, "FULL_QKV": 1 << 6, "VALU_ATTENTION": 1 << 7, "CES_GENERIC": 1 << 9,
        "FUSED_STAMPS": 1 << 10, "NO_BWD_IMAGE_RECOMPUTE": 1 << 11, "NO_BWD_KV_SPARSE": 1 << 12, "SELECT_WORKGROUP": 1 << 13, "S3_SELECT_KERNEL": 1 << 14, "DISABLE_X1": 1 << 15,
        "NO_BWD_TAIL": 1 << 16, "NO_BWD_ATTN_BLOCK": 1 << 17, "NO_BWD_ACQ": 1 << 18, "NO_BWD_LAYER_FWD": 1 << 19,

@@ -1489,13 +1489,71 @@ int gemm_dx(const BCtx &c, const float *dY, int ldy, const float *W, int N, int 
   return ALINE_OK;
 }
 
+// Which kernel takes the weight-gradient product dW[N, K] += dY^T X of a model (gemm_dw, aline_backward_dw_kernel_name): the exact-fp32
+// block kernel, the scaled f16 split on 256 x 256 blocks, or its narrow-tile instantiations (backward.h) where a dimension is a multiple
+// of 128 only -- every encoder product at d = 128, the 128-wide ones of d = 512 / F = 128.  ALINE_DBG_NO_BWD_DW_NARROW: those on the fp32 kernel.
+enum { DW_FP32 = 0, DW_F16_256, DW_F16_NARROW };
+static bool dw_narrow_on() { return !dbg(ALINE_DBG_NO_BWD_DW_NARROW); }
+static int dw_kernel_kind(const aline_model &m, int N, int K, int Ry, int Gy, int ldy, int ldx, long M) {
+  if (!bwd_grad_f16(m) || Ry != Gy || N % 128 || K % 128 || ldy % 4 || ldx % 4 || M >= (1l << 40)) return DW_FP32;
+  if (N % 256 == 0 && K % 256 == 0) return DW_F16_256;
+  return dw_narrow_on() ? DW_F16_NARROW : DW_FP32;
+}
+// block of a narrow product: 128 x 128 everywhere.  (256 along a dimension that is a multiple of 256 -- 8-wave workgroups, one per CU --
+// measured no faster on any shape and 6 - 8 % slower at [256 x 128] / [128 x 256]: DESIGN.md section 7.)
+constexpr int DW_NARROW_TA = 128, DW_NARROW_TB = 128;
+
+// the narrow-tile launch: f is complete but for the blocks and the row chunks
+template <int TA, int TB>
+static int launch_dw_narrow(const BCtx &c, GemmTnF16Args f, int N, int K) {
+  constexpr int THREADS = (TA / 64) * (TB / 64) * 64, LDS = 2 * 2 * (TA + TB) * 32 * 2;      // two images x (hi | lo) x [TA + TB columns][32 rows] f16
+  const void *fn = reinterpret_cast<const void *>(&gemm_tn_f16_narrow_kernel<TA, TB>);
+  // workgroups resident at a time (more than one per CU at 128 x 128): from the occupancy query, once per instantiation and process
+  static std::atomic<long> resident_cache{0};
+  long resident = resident_cache.load(std::memory_order_relaxed);
+  if (resident == 0) {
+    int dev = 0, n_cu = 256, per_cu = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, THREADS, LDS) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    resident = (long)n_cu * per_cu;
+    resident_cache.store(resident, std::memory_order_relaxed);
+  }
+  f.nba = N / TA; f.nbb = K / TB;
+  // rows per workgroup: whole rounds of resident workgroups, the smallest number of rounds that keeps a chunk <= 4096 rows (as gemm_dw)
+  const long nblk = (long)f.nba * f.nbb;
+  long r = 1;
+  while ((f.M * nblk + resident * r - 1) / (resident * r) > 4096) ++r;
+  const long per = (f.M * nblk + resident * r - 1) / (resident * r);
+  f.mchunk = std::max<long>(256, (per + 31) / 32 * 32);
+  f.gx = (int)((f.M + f.mchunk - 1) / f.mchunk);
+  const unsigned grid = (unsigned)((f.gx + 7) / 8 * 8) * (unsigned)nblk;
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  hipLaunchKernelGGL((gemm_tn_f16_narrow_kernel<TA, TB>), dim3(grid), dim3(THREADS), LDS, c.st, f);
+  CHECK_LAUNCH();
+  return ALINE_OK;
+}
+
 // dW[N, K] += dY^T X, db[N] += colsum(dY)
 int gemm_dw(const BCtx &c, const float *dY, int ldy, const float *X, int ldx, float *dW, float *db, long M,
             int N, int K, int Ry = 1, int Gy = 1, int offy = 0, int Rx = 1, int Gx = 1, int offx = 0, int ldw = 0,
             const unsigned *scale = nullptr, const int *row_index = nullptr) {
   if (N % 32 || K % 32) return ALINE_EUNSUPPORTED;
-  if (row_index && !(scale && bwd_grad_f16(*c.m) && N % 256 == 0 && K % 256 == 0)) return ALINE_EUNSUPPORTED;      // (callers check: the f16 block kernel only)
-  if (bwd_grad_f16(*c.m) && Ry == Gy && N % 256 == 0 && K % 256 == 0 && ldy % 4 == 0 && ldx % 4 == 0 && M < (1l << 40)) {
+  const int kind = dw_kernel_kind(*c.m, N, K, Ry, Gy, ldy, ldx, M);
+  const bool aligned = !(reinterpret_cast<uintptr_t>(dY + (long)offy * ldy) & 15) && !(reinterpret_cast<uintptr_t>(X) & 15);
+  if (row_index && !(scale && kind != DW_FP32)) return ALINE_EUNSUPPORTED;      // (callers check: the f16 block kernels only)
+  if (kind == DW_F16_NARROW && aligned) {
+    // X may be row-mapped (the point / target rows of every instance: the first layers of the heads), dY is dense
+    const float *pY = dY + (long)offy * ldy;
+    GemmTnF16Args f{};
+    f.Rp = 1; f.Gp = 1; f.offp = 0; f.Rq = Rx; f.Gq = Gx; f.offq = offx;
+    f.xmax_bits = scale ? scale : grad_absmax(c, pY, M, N, ldy);
+    f.P = pY; f.ldp = ldy; f.Q = X; f.ldq = ldx; f.out = dW; f.sa = ldw > 0 ? ldw : K; f.sb = 1; f.grad_is_p = 1;
+    f.colsum = db; f.M = M; f.row_index = row_index;
+    return launch_dw_narrow<DW_NARROW_TA, DW_NARROW_TB>(c, f, N, K);
+  }
+  if (kind == DW_F16_256) {
     // the scaled 3-term f16 split on 256 x 256 blocks (backward.h: gemm_tn_f16_kernel); X may be row-mapped (the point rows of every
     // instance: the acquisition head's first layer), dY is dense
     const float *pY = dY + (long)offy * ldy, *pX = X;
@@ -1850,7 +1908,7 @@ static ChunkFwd chunk_fwd(const aline_model &m, const aline_rollout &r, int stag
   // The same key list on the way back: dK / dV are zero outside the key rows, so the in-projection's gradient products split into a
   // dense Q part (a third of the columns) and a K | V part over the key rows only (gathered by the list; dX scattered back)
   f.kv_sparse = do_enc && !f.ckv && bwd_grad_f16(m) && !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) && !dbg(ALINE_DBG_NO_BWD_KV_SPARSE) &&
-                (hd == 32 || hd == 64) && max_keys <= 48 && max_keys < N && d % 256 == 0;
+                (hd == 32 || hd == 64) && max_keys <= 48 && max_keys < N && d % (dw_narrow_on() ? 128 : 256) == 0;      // (the K | V part [2 d x d] needs an f16 block kernel: gemm_dw)
   return f;
 }
 
@@ -2330,6 +2388,14 @@ extern "C" int aline_backward_recompute_name(const aline_model *m, const aline_r
   }
   else snprintf(buf, n, "generic");
   return cf.rc_q ? 1 : 0;
+}
+
+extern "C" int aline_backward_dw_kernel_name(const aline_model *m, int N, int K, char *buf, size_t n) {
+  if (!m || !buf || n == 0 || N < 1 || K < 1) return ALINE_EINVAL;
+  const int kind = dw_kernel_kind(*m, N, K, 1, 1, N, K, 1);      // (dense, aligned operands)
+  if (kind == DW_F16_NARROW) snprintf(buf, n, "gemm_tn_f16_narrow_kernel<%d, %d>", DW_NARROW_TA, DW_NARROW_TB);
+  else snprintf(buf, n, "%s", kind == DW_F16_256 ? "gemm_tn_f16_kernel" : "gemm_tn_block_kernel");
+  return kind == DW_FP32 ? 0 : 1;
 }
 
 extern "C" int aline_rollout_backward_ex(const aline_model *m, const aline_rollout *r, const float *g_logp,

@@ -431,6 +431,151 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_f16_kernel(GemmTnF16Args a) {
   }
 }
 
+// ---- the same product for gradients that are 128 wide in a dimension (d = 128 layers, F = 128 heads) -----------------------------------
+// out[a, b] += sum_m P[m, a0 + a] * Q[m, b0 + b] for a TA x TB block, (TA, TB) in {128, 256}^2 without (256, 256) -- that is the kernel
+// above.  Same arithmetic, same LDS image ([column][32 rows] f16, hi | lo planes, gemm_swz), same scale, row maps, index list and column
+// sums; another split of the work, because these products are bound by the operand stream and not by the matrix pipe: a product row
+// moves (N + K) * 4 bytes for 2 N K FLOP -- 32 FLOP/B at [128 x 128], 51 at [512 x 128] -- below the f16-split MFMA ceiling at the HBM rate.
+//   * a wave owns 64 x 64 of the block (16 accumulator tiles: 64 registers where the kernel above holds 128), so a 128 x 128 block is a
+//     4-wave workgroup with two 32 KB images (64 KB): two workgroups fit a CU and cover each other's slab barrier
+//   * staging tasks are [8 rows x 4 columns] as above -- TA + TB of them per slab, one per thread of the first (TA + TB) / 64 waves (all
+//     four of a 128 x 128 block).  A wave covers two row groups of a 128-wide tile: 512 B of a row per half wave and instruction
+//   * one barrier per slab, slab s + 1 stored and slab s + 2 requested behind the first quarter of the MFMAs of slab s
+// Only <128, 128> is instantiated (gemm_dw).  The 8-wave blocks <256, 128> / <128, 256> (two 48 KB images, one workgroup per CU, six of
+// eight waves staging) were built from this template and measured: no faster on any shape, 6 - 8 % slower at [256 x 128] and
+// [128 x 256]; 1.5 M rows of [128 x 128] take 0.45 ms (fp32 block kernel: 0.54), of [512 x 128] 0.99 ms (1.86).
+template <int TA, int TB>
+__global__ __launch_bounds__((TA / 64) * (TB / 64) * 64, 2) void gemm_tn_f16_narrow_kernel(GemmTnF16Args a) {
+  static_assert((TA == 128 || TA == 256) && (TB == 128 || TB == 256) && TA + TB < 512, "256 x 256 blocks: gemm_tn_f16_kernel");
+  constexpr int COLS = TA + TB, PLANE = COLS * 32, WA = TA / 64;          // f16 elements per plane; waves along a
+  extern __shared__ __attribute__((aligned(16))) unsigned short tn_smem[];     // 2 images x (hi | lo) x COLS x 64 B
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fg = lane >> 4;
+  // workgroup order as above: the blocks of one row chunk on one XCD at about the same time
+  const unsigned nb_all = (unsigned)(a.nba * a.nbb), per = 8u * nb_all;
+  const unsigned grp = blockIdx.x / per, within = blockIdx.x - grp * per;
+  const long chunk = (long)grp * 8 + (within & 7u);
+  const int nb = (int)(within >> 3);
+  if (chunk >= a.gx) return;
+  const int ba = nb % a.nba, bb = nb / a.nba;
+  const long m_lo = chunk * a.mchunk, m_hi = min(a.M, m_lo + a.mchunk);
+  float xinv = 1.f;
+  const float xscale = f16_operand_scale(*a.xmax_bits, xinv);
+  // staging task of this thread: 4 consecutive columns x 8 rows of the combined [32 x COLS] slab (tid < COLS; P's tasks first)
+  const bool stager = tid < COLS, is_p = tid < TA;                 // (wave-uniform: TA and COLS are multiples of 64)
+  const int t = is_p ? tid : tid - TA;
+  const int c4 = 4 * (t % ((is_p ? TA : TB) / 4));                 // first of the 4 columns inside the operand's tile
+  const int rg = t / ((is_p ? TA : TB) / 4);                       // row group 0 .. 3 (rows 8 rg .. 8 rg + 7 of the slab)
+  const float *src = is_p ? a.P + (long)ba * TA + c4 : a.Q + (long)bb * TB + c4;
+  const int ld = is_p ? a.ldp : a.ldq;
+  const bool is_grad = is_p == (a.grad_is_p != 0);
+  const float sc = is_grad ? xscale : 1.f;
+  const int ccol = (is_p ? 0 : TA) + c4;                           // column of the LDS image
+  float4 v[8];
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};
+  const int mapR = is_p ? a.Rp : a.Rq, mapG = is_p ? a.Gp : a.Gq, mapOff = is_p ? a.offp : a.offq;
+  auto load_slab = [&](long m0) {
+    if (!stager) return;
+    const long first = m0 + 8 * rg;
+    if (a.row_index) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int ri = first + e < m_hi ? a.row_index[first + e] : -1;
+        v[e] = ri >= 0 ? *reinterpret_cast<const float4 *>(src + (long)ri * ld) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      return;
+    }
+    long q = 0;
+    int r = 0;
+    if (mapR != mapG) { q = first / mapR; r = (int)(first - q * mapR); }      // one division per 8 rows, then a walked remainder
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const long m = first + e;
+      const long row = mapR == mapG ? m + mapOff : q * mapG + mapOff + r;
+      v[e] = m < m_hi ? *reinterpret_cast<const float4 *>(src + row * ld) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (++r == mapR) { r = 0; ++q; }
+    }
+  };
+  auto store_slab = [&](unsigned short *smem) {
+    if (!stager) return;
+    if (is_grad) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { cs[0] += v[e].x; cs[1] += v[e].y; cs[2] += v[e].z; cs[3] += v[e].w; }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      typedef __attribute__((ext_vector_type(4))) unsigned tn_u32x4;
+      tn_u32x4 h, l;
+#pragma unroll
+      for (int e2 = 0; e2 < 4; ++e2) {
+        const float x0 = (q == 0 ? v[2 * e2].x : q == 1 ? v[2 * e2].y : q == 2 ? v[2 * e2].z : v[2 * e2].w) * sc;
+        const float x1 = (q == 0 ? v[2 * e2 + 1].x : q == 1 ? v[2 * e2 + 1].y : q == 2 ? v[2 * e2 + 1].z : v[2 * e2 + 1].w) * sc;
+        unsigned hh, ll;
+        split2_f16(x0, x1, hh, ll);
+        h[e2] = hh; l[e2] = ll;
+      }
+      const int off = gemm_swz(ccol + q, 8 * rg);
+      *reinterpret_cast<tn_u32x4 *>(smem + off) = h;
+      *reinterpret_cast<tn_u32x4 *>(smem + PLANE + off) = l;
+    }
+  };
+  // MFMA tiles of this wave: P tiles 4 wi .. 4 wi + 3 (rows of the block), Q tiles 4 wj .. 4 wj + 3 (columns)
+  const int wi = wave % WA, wj = wave / WA;
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  load_slab(m_lo);
+  store_slab(tn_smem);
+  __syncthreads();
+  if (m_lo + 32 < m_hi) load_slab(m_lo + 32);
+  int buf = 0;
+  for (long m0 = m_lo; m0 < m_hi; m0 += 32, buf ^= 1) {
+    const unsigned short *smem = tn_smem + buf * 2 * PLANE;
+    gemm_f16x8 ah[4], al[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int off = gemm_swz(64 * wi + 16 * i + fr, 8 * fg);
+      ah[i] = *reinterpret_cast<const gemm_f16x8 *>(smem + off);
+      al[i] = *reinterpret_cast<const gemm_f16x8 *>(smem + PLANE + off);
+    }
+    auto mul = [&](int j) {
+      const int off = gemm_swz(TA + 64 * wj + 16 * j + fr, 8 * fg);
+      const gemm_f16x8 bh = *reinterpret_cast<const gemm_f16x8 *>(smem + off);
+      const gemm_f16x8 bl = *reinterpret_cast<const gemm_f16x8 *>(smem + PLANE + off);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh, acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl, acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+      }
+    };
+    mul(0);
+    // the next slab (its loads were issued a slab ago) goes into the other image -- every wave left it at the last barrier --,
+    // then the loads of the slab after it
+    if (m0 + 32 < m_hi) store_slab(tn_smem + (buf ^ 1) * 2 * PLANE);
+    if (m0 + 64 < m_hi) load_slab(m0 + 64);
+#pragma unroll
+    for (int j = 1; j < 4; ++j) mul(j);
+    __syncthreads();
+  }
+  // every element of the block belongs to one lane of one wave: acc[i][j][r] is (a, b) = (64 wi + 16 i + 4 fg + r, 64 wj + 16 j + fr)
+  float *o = a.out + ((long)ba * TA + 64 * wi + 4 * fg) * a.sa + ((long)bb * TB + 64 * wj + fr) * a.sb;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) atomicAdd(o + (long)(16 * i + r) * a.sa + (long)(16 * j) * a.sb, acc[i][j][r] * xinv);
+  // bias gradient: column sums of the gradient operand, once per row chunk (by the blocks with index 0 along the other operand)
+  if (a.colsum && stager && is_grad && (is_p ? bb == 0 : ba == 0)) {
+    float *dst = a.colsum + (long)(is_p ? ba * TA : bb * TB) + c4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) atomicAdd(dst + q, cs[q]);
+  }
+}
+
 // LayerNorm backward (post-norm block): y = LN(u) * w + b.
 //   dU = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dY * w;  dw += dY * xhat;  db += dY
 // One wave per row; per-workgroup partial dw/db through LDS, then one atomic per feature.

@@ -200,6 +200,10 @@ int aline_rollout_kernel_name(const aline_model *m, const aline_rollout *r, char
  * rollout) or "generic";
  * returns 1 if Q comes from that kernel too (rc_q), else 0; negative on error.  Host logic only. */
 int aline_backward_recompute_name(const aline_model *m, const aline_rollout *r, int t0, int nt, char *buf, size_t n);
+/* the kernel that takes the weight-gradient product dW[N, K] += dY^T X of a training backward of m for dense, 16-byte aligned operands:
+ * "gemm_tn_block_kernel" (exact fp32), "gemm_tn_f16_kernel" (256 x 256 blocks) or "gemm_tn_f16_narrow_kernel<128, 128>" (a dimension a multiple of 128 only);
+ * returns 1 for an f16 kernel, 0 for the fp32 one; negative on error.  Host logic only. */
+int aline_backward_dw_kernel_name(const aline_model *m, int N, int K, char *buf, size_t n);
 /* Task.update_batch equivalent for callers that want the reference layout back
  * (tasks/base_task.py:133-154): context_x/y [B,n_ctx0+T,*] in order of entry, query remainder. */
 int aline_rollout_export(const aline_rollout *r, int n_ctx, float *context_x, float *context_y,
@@ -316,6 +320,7 @@ int aline_f16_range_status(const void *ws, void *stream);
 /* Process-wide diagnostic word, 0 in normal operation.  Tests and A/B measurements use it to force the path a fused kernel
  * replaces (every fused kernel is cross-checked against that path) or to opt into an experiment.  Returns the old word. */
 enum { ALINE_DBG_DISABLE_FUSED = 1u << 0,      /* fused::rollout_f32_kernel off -> generic pipeline */
+       ALINE_DBG_NO_BWD_DW_NARROW = 1u << 1,   /* weight-gradient products with a dimension that is a multiple of 128 only: the exact-fp32 block kernel instead of gemm_tn_f16_narrow_kernel, and kv_sparse at multiples of 256 only */
        ALINE_DBG_DISABLE_X3 = 1u << 2,         /* x3 path off -> generic pipeline on the F16X3 GEMM policy */
        ALINE_DBG_DISABLE_S3 = 1u << 3,         /* s3 path off */
        ALINE_DBG_NO_LAYER_TAIL = 1u << 5,      /* generic d = 32 pipeline on per-op kernels */

@@ -143,13 +143,15 @@ def run_train_pairs(name, model, batch, T, steps, pairs, flag="NO_BWD_IMAGE_RECO
     """Same-box alternating pairs: ms per `train_step` (sampled rollout, REINFORCE terms, backward, optimiser) with the library's default
     backward and with the diagnostic switch `flag` set -- the generic forward recompute, which is what the library did for this shape before
     the layer kernel's SAVE variant.  One JSON line per pair; which kernel recomputes the chunks is reported by the library.
-    (pairs = 0: timed steps of the default only -- the form a run on another build of the library takes, ALINE_HIP_LIB.)"""
+    (pairs = 0: timed steps of the default only -- the form a run on another build of the library takes, ALINE_HIP_LIB.)
+    --train-flag NO_BWD_DW_NARROW: the other side is the weight-gradient dispatch before the narrow-tile f16 kernel (fp32 block kernel)."""
     import ctypes
     from aline_amd import _lib
     from aline_amd.train import train_step
     opt = torch.optim.Adam(model.parameters(), lr=1e-5)
     names = {}
-    for k, flags in (("default", []), ("generic_recompute", [flag])):
+    other = "generic_recompute" if flag == "NO_BWD_IMAGE_RECOMPUTE" else flag.lower()
+    for k, flags in (("default", []), (other, [flag])):
         with _lib.debug(*flags):
             for _ in range(2):                              # warm-up of both sides: code objects, graph cache, workspace
                 _, ro = train_step(model, batch, T, optimizer=opt)
@@ -163,12 +165,12 @@ def run_train_pairs(name, model, batch, T, steps, pairs, flag="NO_BWD_IMAGE_RECO
         return
     for i in range(pairs):
         ms = {}
-        for k, flags in (("default", []), ("generic_recompute", [flag])):
+        for k, flags in (("default", []), (other, [flag])):
             with _lib.debug(*flags):
                 ms[k] = timed_train_steps(model, batch, T, opt, steps)
         print(json.dumps({"config": name, "pair": i, "B": int(ro.B), "T": T, "default_ms_per_train_step": round(ms["default"], 2),
-                          "generic_recompute_ms_per_train_step": round(ms["generic_recompute"], 2),
-                          "ratio": round(ms["generic_recompute"] / ms["default"], 4), "recompute": names}), flush=True)
+                          f"{other}_ms_per_train_step": round(ms[other], 2),
+                          "ratio": round(ms[other] / ms["default"], 4), "recompute": names}), flush=True)
 
 
 def main():
@@ -177,6 +179,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--precs", default="", help="comma list: only these precisions (default: all)")
     ap.add_argument("--pairs", type=int, default=5, help="3w / 1w: alternating pairs")
+    ap.add_argument("--train-flag", default="NO_BWD_IMAGE_RECOMPUTE", help="1wt / 5t: the diagnostic switch of the other side of a pair")
     args = ap.parse_args()
     global ONLY_PRECS
     ONLY_PRECS = set(args.precs.split(",")) if args.precs else None
@@ -228,7 +231,12 @@ def main():
     if "1wt" in want:
         batch = HiddenLocation(n_query_init=200, device=dev).sample_batch(1000)
         run_train_pairs("headline geometry at d=128 F=512 H=4 f16x3: location_finding B=1000 T=30, train_step",
-                        build(2, 128, 512, 4, 2, "theta", "f16x3"), batch, 30, args.steps, args.pairs)
+                        build(2, 128, 512, 4, 2, "theta", "f16x3"), batch, 30, args.steps, args.pairs, args.train_flag)
+    if "5t" in want:      # the training leg of cfg5 at F = 128 (its 128-wide weight-gradient products), pairs against --train-flag
+        batch = PsychometricTask(n_query_init=200, n_context_init=1, device=dev).sample_batch(256)
+        batch["target_mask"] = torch.tensor([False, False, True, True])
+        run_train_pairs("cfg5 psychometric B=256 T=30 d=512 F=128 H=8 f16x3, predefined mask, train_step",
+                        build(1, 512, 128, 8, 4, "theta", "f16x3"), batch, 30, args.steps, args.pairs, args.train_flag)
     if "5" in want:
         task = PsychometricTask(n_query_init=200, n_context_init=1, device=dev)
         batch = task.sample_batch(256)
