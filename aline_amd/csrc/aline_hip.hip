@@ -15,6 +15,7 @@
 #include "backward.h"
 #include "attn_bwd_wide.h"
 #include "attn_bwd_long.h"
+#include "attn_bwd_long64.h"
 #include "attn_bwd8.h"
 #include "tail_bwd.h"
 #include "attn_bwd_mfma.h"
@@ -1683,6 +1684,22 @@ static int launch_attention_bwd_long(const BCtx &c, const float *qkv, const floa
   return ALINE_OK;
 }
 
+// head_dim 64, 49 - 160 keys on the f16 matrix pipe, at most two key tiles per wave, operands streamed from split row images
+// (attn_bwd_long64.h).  LDS: 146 080 bytes at most (<2, 4>) + 8 per padded token row: N <= 2208 rows in every shape
+static size_t attention_bwd_long64_lds(int nkt, int N) {
+  return nkt <= 4 ? abwl64::lds_bytes(1, 4, N) : nkt <= 8 ? abwl64::lds_bytes(2, 4, N) : abwl64::lds_bytes(2, 8, N);
+}
+template <int TPW, int G>
+static int launch_attention_bwd_long64(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, unsigned *mw,
+                                       const unsigned *da_scale) {
+  const size_t smem = abwl64::lds_bytes(TPW, G, c.g.N);
+  if (smem > 160 * 1024) return ALINE_EUNSUPPORTED;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&abwl64::attention_bwd_long64_kernel<TPW, G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL((abwl64::attention_bwd_long64_kernel<TPW, G>), dim3((unsigned)c.g.B), dim3(64 * abwl64::WAVES), smem, c.st, c.g, c.m->d, qkv, dA, aout, dqkv, mw, da_scale);
+  CHECK_LAUNCH();
+  return ALINE_OK;
+}
+
 template <int NKT>
 static int launch_attention_bwd8(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, const unsigned *da_scale) {
   const size_t smem = abw8::lds_bytes(NKT, c.g.N);
@@ -1696,7 +1713,9 @@ static int launch_attention_bwd8(const BCtx &c, const float *qkv, const float *d
 // Which matrix-pipe attention backward serves head_dim hd at max_keys keys, given the attention output and (have_da_scale) the scale word
 // of dA: ABW_WIDE (attn_bwd_wide.h: <= 3 key tiles), ABW_LONG (attn_bwd_long.h: 4 - 10 key tiles at head_dim 32 of a model whose gradient
 // products run on the f16 pipe), or ABW_NONE.  Both kernels read K / V of the key rows only -- the forward recompute decides by this
-// whether Q may come from the layer kernel (backward_impl: rc_q).
+// whether Q may come from the layer kernel (backward_impl: rc_q).  The head_dim-64 twin of ABW_LONG (attn_bwd_long64.h) is NOT a class of
+// this predicate but has its own below (attn_bwd_long64_serves): the recompute in front of it keeps filling Q / K / V of every row by the
+// in-projection GEMM, as it does in front of the VALU kernel.
 enum { ABW_NONE = 0, ABW_WIDE, ABW_LONG };
 static int attn_bwd_matrix_pipe(const aline_model &m, int hd, int max_keys, bool have_aout, bool have_da_scale) {
   if (dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) || !have_aout || (hd != 32 && hd != 64) || m.d % hd != 0) return ABW_NONE;      // (the switch: the VALU kernel, A/B measurements)
@@ -1704,6 +1723,13 @@ static int attn_bwd_matrix_pipe(const aline_model &m, int hd, int max_keys, bool
   if (nkt <= 3) return ABW_WIDE;      // (<32, 4> spills 64 registers: beyond 48 keys the kernels below)
   if (hd == 32 && have_da_scale && nkt <= 10 && bwd_grad_f16(m)) return ABW_LONG;
   return ABW_NONE;
+}
+
+// head_dim 64, 4 - 10 key tiles, under ABW_LONG's conditions and within the kernel's LDS (beyond it: the VALU kernel if that fits)
+static bool attn_bwd_long64_serves(const aline_model &m, int hd, int max_keys, int N, bool have_aout, bool have_da_scale) {
+  const int nkt = (max_keys + 15) / 16;
+  return hd == 64 && m.d % 64 == 0 && nkt >= 4 && nkt <= 10 && have_aout && have_da_scale && bwd_grad_f16(m) && !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) &&
+         attention_bwd_long64_lds(nkt, N) <= 160 * 1024;
 }
 
 template <int HD>
@@ -1751,6 +1777,19 @@ int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float
       if (nkt <= 6) return launch_attention_bwd_long<3, 2>(c, qkv, dA, aout, dqkv, mw, da_scale);
       if (nkt <= 8) return launch_attention_bwd_long<2, 4>(c, qkv, dA, aout, dqkv, mw, da_scale);
       return launch_attention_bwd_long<3, 4>(c, qkv, dA, aout, dqkv, mw, da_scale);
+    }
+  }
+  if constexpr (HD == 64) {
+    // 4 - 10 key tiles of an F16X3 model, given the scale word of dA: at most two key tiles per wave (attn_bwd_long64.h).  The pick per
+    // tile count: DESIGN.md 7 (<1, 8> for 5 - 8 tiles was not built: one head per round doubles the rounds of barriers)
+    if (attn_bwd_long64_serves(*c.m, HD, max_keys, c.g.N, aout != nullptr, da_scale != nullptr)) {
+      const int nkt = (max_keys + 15) / 16;
+      if (key_rows_only) return ALINE_EUNSUPPORTED;      // (kv_sparse ends at 48 keys: the kernel writes whole rows)
+      unsigned *mw = out_max ? new_scale_word(c) : nullptr;
+      if (out_max) *out_max = mw;
+      if (nkt == 4) return launch_attention_bwd_long64<1, 4>(c, qkv, dA, aout, dqkv, mw, da_scale);
+      if (nkt <= 8) return launch_attention_bwd_long64<2, 4>(c, qkv, dA, aout, dqkv, mw, da_scale);
+      return launch_attention_bwd_long64<2, 8>(c, qkv, dA, aout, dqkv, mw, da_scale);
     }
   }
   if (mfma_on && HD == abwd::HD && c.m->d == abwd::D && max_keys <= abwd::MAXK) {
