@@ -98,6 +98,7 @@ def _load():
         "aline_rollout_kernel_name": (C.c_int, [MP, RP, C.c_char_p, C.c_size_t]),
         "aline_backward_recompute_name": (C.c_int, [MP, RP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
         "aline_backward_dw_kernel_name": (C.c_int, [MP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+        "aline_backward_attn_kernel_name": (C.c_int, [MP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
         "aline_rollout_export": (C.c_int, [RP, C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp]),
         "aline_compute_ll": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int, _fp, _fp]),
         "aline_eig_location_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_int,

@@ -17,6 +17,7 @@
 #include "attn_bwd_long.h"
 #include "attn_bwd_long64.h"
 #include "attn_bwd8.h"
+#include "attn_bwd16.h"
 #include "tail_bwd.h"
 #include "attn_bwd_mfma.h"
 #include "acq_head_bwd.h"
@@ -1673,6 +1674,9 @@ static int launch_attention_bwd_wide(const BCtx &c, const float *qkv, const floa
 
 // head_dim 32, 49 - 160 keys on the f16 matrix pipe, a head's key tiles split over G waves (attn_bwd_long.h).  Its LDS holds the key list
 // and 8 bytes per padded token row beside the fixed blocks (92 KB at most, <3, 2>): N <= 8736 rows in every shape, beyond its limit a shape is refused
+static size_t attention_bwd_long_lds(int nkt, int N) {
+  return nkt == 4 ? abwl::lds_bytes(2, 2, N) : nkt <= 6 ? abwl::lds_bytes(3, 2, N) : nkt <= 8 ? abwl::lds_bytes(2, 4, N) : abwl::lds_bytes(3, 4, N);
+}
 template <int TPW, int G>
 static int launch_attention_bwd_long(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, unsigned *mw,
                                      const unsigned *da_scale) {
@@ -1700,6 +1704,20 @@ static int launch_attention_bwd_long64(const BCtx &c, const float *qkv, const fl
   return ALINE_OK;
 }
 
+// head_dim 16, 1 - 160 keys on the f16 matrix pipe, two waves per head, the row side streamed (attn_bwd16.h).  LDS: 152 736 bytes at
+// ten key tiles + 1 per padded token row
+template <int NKT>
+static int launch_attention_bwd16(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, unsigned *mw,
+                                  const unsigned *da_scale) {
+  const size_t smem = abw16::lds_bytes(NKT, c.g.N);
+  if (smem > 160 * 1024) return ALINE_EUNSUPPORTED;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&abw16::attention_bwd16_kernel<NKT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL((abw16::attention_bwd16_kernel<NKT>), dim3((unsigned)c.g.B), dim3(64 * abw16::WAVES), smem, c.st, c.g, c.m->d, qkv, dA, aout, dqkv, mw, da_scale);
+  CHECK_LAUNCH();
+  return ALINE_OK;
+}
+
+static int attention_bwd8_nkt(int max_keys) { return max_keys <= 64 ? 4 : max_keys <= 112 ? 7 : 10; }
 template <int NKT>
 static int launch_attention_bwd8(const BCtx &c, const float *qkv, const float *dA, const float *aout, float *dqkv, const unsigned *da_scale) {
   const size_t smem = abw8::lds_bytes(NKT, c.g.N);
@@ -1732,19 +1750,62 @@ static bool attn_bwd_long64_serves(const aline_model &m, int hd, int max_keys, i
          attention_bwd_long64_lds(nkt, N) <= 160 * 1024;
 }
 
+// d = 32 / 4 heads of 8 beyond the fused attention block's 48 keys (cfg3), given the attention output and the scale word of dA (attn_bwd8.h)
+static bool attn_bwd8_serves(const aline_model &m, int hd, int max_keys, bool have_aout, bool have_da_scale) {
+  return hd == 8 && !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) && have_aout && have_da_scale && m.d == 32 && m.H == 4 && max_keys <= 160 &&
+         m.precision == ALINE_PREC_F16X3 && !dbg(ALINE_DBG_BWD_GRAD_F32);
+}
+
+// head_dim 16, 1 - 160 keys of a model whose gradient products run on the f16 pipe, within the kernel's LDS (attn_bwd16.h; beyond it: the
+// VALU kernel if that fits).  Like attn_bwd_long64_serves no class of attn_bwd_matrix_pipe: rc_q and the recompute stay as they were.
+static bool attn_bwd16_serves(const aline_model &m, int hd, int max_keys, int N, bool have_aout, bool have_da_scale) {
+  return hd == 16 && m.d % 16 == 0 && max_keys >= 1 && max_keys <= 160 && have_aout && have_da_scale && bwd_grad_f16(m) &&
+         !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) && abw16::lds_bytes(abw16::nkt_for(max_keys), N) <= 160 * 1024;
+}
+
+// The fused in-projection + attention kernel's attention part alone (attn_bwd_mfma.h)
+static bool attn_bwd_mfma_serves(const aline_model &m, int hd, int max_keys) {
+  return !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) && hd == abwd::HD && m.d == abwd::D && max_keys <= abwd::MAXK;
+}
+
+// The fp32 VALU kernel (backward.h): threads, whether dK / dV take the place of K / V in LDS, and its LDS bytes -- K, V (+ the dK / dV sums
+// where they cannot take their place), key list | scaled Q, dO, row statistics of every row
+struct AttnBwdValu { int nthr; bool reuse; size_t smem; };
+static AttnBwdValu attn_bwd_valu(int hd, int max_keys, int N) {
+  AttnBwdValu v;
+  v.nthr = hd <= 16 ? std::min(512, std::max(256, (N + 63) / 64 * 64)) : 256;      // whole waves of token rows
+  v.reuse = hd <= 16 && max_keys <= v.nthr;
+  v.smem = (size_t)max_keys * ((v.reuse ? 2 : 4) * hd * sizeof(float) + sizeof(int)) + (size_t)N * (2 * hd + 4) * sizeof(float);
+  return v;
+}
+static bool attn_bwd_valu_fits(const AttnBwdValu &v) { return v.smem <= 160 * 1024 - 1024; }
+
 template <int HD>
 int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float *dqkv, int max_keys, const float *aout = nullptr,
                          unsigned **out_max = nullptr, bool key_rows_only = false, const unsigned *da_scale = nullptr) {
-  const bool mfma_on = !dbg(ALINE_DBG_NO_BWD_ATTN_MFMA);      // 0: the VALU kernel (A/B measurements)
   const int pipe = attn_bwd_matrix_pipe(*c.m, HD, max_keys, aout != nullptr, da_scale != nullptr);
   if (out_max) *out_max = nullptr;
   if constexpr (HD == 8) {
     // d = 32 / 4 heads beyond the fused attention block's 48 keys (cfg3): the f16 matrix pipe (attn_bwd8.h), given the scale word of dA
-    if (mfma_on && aout && da_scale && c.m->d == 32 && c.m->H == 4 && max_keys <= 160 && c.m->precision == ALINE_PREC_F16X3 &&
-        !dbg(ALINE_DBG_BWD_GRAD_F32)) {
-      if (max_keys <= 64) return launch_attention_bwd8<4>(c, qkv, dA, aout, dqkv, da_scale);
-      if (max_keys <= 112) return launch_attention_bwd8<7>(c, qkv, dA, aout, dqkv, da_scale);
-      return launch_attention_bwd8<10>(c, qkv, dA, aout, dqkv, da_scale);
+    if (attn_bwd8_serves(*c.m, HD, max_keys, aout != nullptr, da_scale != nullptr)) {
+      switch (attention_bwd8_nkt(max_keys)) {
+        case 4: return launch_attention_bwd8<4>(c, qkv, dA, aout, dqkv, da_scale);
+        case 7: return launch_attention_bwd8<7>(c, qkv, dA, aout, dqkv, da_scale);
+        default: return launch_attention_bwd8<10>(c, qkv, dA, aout, dqkv, da_scale);
+      }
+    }
+  }
+  if constexpr (HD == 16) {
+    // heads of 16 channels of an F16X3 model, given the scale word of dA: two waves per head, the row side streamed (attn_bwd16.h)
+    if (attn_bwd16_serves(*c.m, HD, max_keys, c.g.N, aout != nullptr, da_scale != nullptr)) {
+      if (key_rows_only) return ALINE_EUNSUPPORTED;      // (kv_sparse is never on at head_dim 16: the kernel writes whole rows)
+      unsigned *mw = out_max ? new_scale_word(c) : nullptr;
+      if (out_max) *out_max = mw;
+      switch (abw16::nkt_for(max_keys)) {
+        case 4: return launch_attention_bwd16<4>(c, qkv, dA, aout, dqkv, mw, da_scale);
+        case 7: return launch_attention_bwd16<7>(c, qkv, dA, aout, dqkv, mw, da_scale);
+        default: return launch_attention_bwd16<10>(c, qkv, dA, aout, dqkv, mw, da_scale);
+      }
     }
   }
   if constexpr (HD == 32 || HD == 64) {
@@ -1792,17 +1853,16 @@ int launch_attention_bwd(const BCtx &c, const float *qkv, const float *dA, float
       return launch_attention_bwd_long64<2, 8>(c, qkv, dA, aout, dqkv, mw, da_scale);
     }
   }
-  if (mfma_on && HD == abwd::HD && c.m->d == abwd::D && max_keys <= abwd::MAXK) {
+  if (attn_bwd_mfma_serves(*c.m, HD, max_keys)) {
     hipLaunchKernelGGL(abwd::attention_bwd_mfma_kernel, dim3((unsigned)c.g.B), dim3(abwd::THREADS), 0, c.st, c.g, qkv, dA, dqkv);
     CHECK_LAUNCH();
     return ALINE_OK;
   }
-  const int nthr = HD <= 16 ? std::min(512, std::max(256, (c.g.N + 63) / 64 * 64)) : 256;      // whole waves of token rows
-  // K, V (+ the dK / dV sums where they cannot take their place: backward.h), key list | scaled Q, dO, row statistics
-  const bool reuse = HD <= 16 && max_keys <= nthr;
-  size_t smem = (size_t)max_keys * ((reuse ? 2 : 4) * HD * sizeof(float) + sizeof(int)) +
-                (size_t)c.g.N * (2 * HD + 4) * sizeof(float);
-  if (smem > 160 * 1024 - 1024) return ALINE_EUNSUPPORTED;
+  const AttnBwdValu valu = attn_bwd_valu(HD, max_keys, c.g.N);
+  if (!attn_bwd_valu_fits(valu)) return ALINE_EUNSUPPORTED;
+  const int nthr = valu.nthr;
+  const bool reuse = valu.reuse;
+  const size_t smem = valu.smem;
   const float *ao = dbg(ALINE_DBG_NO_BWD_ATTN_MFMA) ? (const float *)nullptr : aout;
   if constexpr (HD <= 16) {
     if (reuse) {
@@ -2356,7 +2416,7 @@ static int backward_impl(const aline_model *m, const aline_rollout *r, const flo
       switch (hd) {
         case 4: TRY(launch_attention_bwd<4>(c, QKVl(l), dTmp, dQKV, max_keys, Al(l))); break;
         case 8: TRY(launch_attention_bwd<8>(c, QKVl(l), dTmp, dQKV, max_keys, Al(l), nullptr, false, sw_da)); break;
-        case 16: TRY(launch_attention_bwd<16>(c, QKVl(l), dTmp, dQKV, max_keys, Al(l))); break;
+        case 16: TRY(launch_attention_bwd<16>(c, QKVl(l), dTmp, dQKV, max_keys, Al(l), &sw_att, false, sw_da)); break;
         case 32: TRY(launch_attention_bwd<32>(c, QKVl(l), dTmp, dQKV, max_keys, Al(l), &sw_att, kv_sparse, sw_da)); break;
         case 64: TRY(launch_attention_bwd<64>(c, QKVl(l), dTmp, dQKV, max_keys, Al(l), &sw_att, kv_sparse, sw_da)); break;
         default: return ALINE_EUNSUPPORTED;
@@ -2435,6 +2495,36 @@ extern "C" int aline_backward_dw_kernel_name(const aline_model *m, int N, int K,
   if (kind == DW_F16_NARROW) snprintf(buf, n, "gemm_tn_f16_narrow_kernel<%d, %d>", DW_NARROW_TA, DW_NARROW_TB);
   else snprintf(buf, n, "%s", kind == DW_F16_256 ? "gemm_tn_f16_kernel" : "gemm_tn_block_kernel");
   return kind == DW_FP32 ? 0 : 1;
+}
+
+// The choices of launch_attention_bwd in its order, from its own predicates, with the attention output and (F16X3 gradient products) the
+// scale word of dA at hand as in backward_impl
+extern "C" int aline_backward_attn_kernel_name(const aline_model *m, int max_keys, int N, char *buf, size_t n) {
+  if (!m || !buf || n == 0 || max_keys < 1 || N < 1 || m->H < 1 || m->d % m->H != 0) return ALINE_EINVAL;
+  const int hd = m->d / m->H, nkt = (max_keys + 15) / 16;
+  const bool have_scale = bwd_grad_f16(*m) || (hd == 8 && bwd_fused_tail(*m) && m->precision == ALINE_PREC_F16X3 && !dbg(ALINE_DBG_BWD_GRAD_F32));
+  const int pipe = attn_bwd_matrix_pipe(*m, hd, max_keys, true, have_scale);
+  const char *name = nullptr;
+  size_t smem = 0;
+  if (attn_bwd8_serves(*m, hd, max_keys, true, have_scale)) {
+    name = "abw8::attention_bwd8_kernel"; smem = abw8::lds_bytes(attention_bwd8_nkt(max_keys), N);
+  } else if (attn_bwd16_serves(*m, hd, max_keys, N, true, have_scale)) {
+    name = "abw16::attention_bwd16_kernel"; smem = abw16::lds_bytes(abw16::nkt_for(max_keys), N);
+  } else if (pipe == ABW_WIDE) {
+    name = (have_scale && bwd_grad_f16(*m)) ? "abww::attention_bwd_wide16_kernel" : "abww::attention_bwd_wide_kernel";
+    smem = abww::lds_bytes(hd, std::min(nkt, 3), N, std::min((int)m->H, hd == 64 ? 4 : abww::MAXW));
+  } else if (pipe == ABW_LONG) {
+    name = "abwl::attention_bwd_long_kernel"; smem = attention_bwd_long_lds(nkt, N);
+  } else if (attn_bwd_long64_serves(*m, hd, max_keys, N, true, have_scale)) {
+    name = "abwl64::attention_bwd_long64_kernel"; smem = attention_bwd_long64_lds(nkt, N);
+  } else if (attn_bwd_mfma_serves(*m, hd, max_keys)) {
+    name = "abwd::attention_bwd_mfma_kernel";
+  } else if (hd == 4 || hd == 8 || hd == 16 || hd == 32 || hd == 64) {
+    const AttnBwdValu valu = attn_bwd_valu(hd, max_keys, N);
+    name = "attention_bwd_kernel"; smem = attn_bwd_valu_fits(valu) ? 0 : (size_t)-1;
+  }
+  snprintf(buf, n, "%s", name && smem <= 160 * 1024 ? name : "unsupported");
+  return ALINE_OK;
 }
 
 extern "C" int aline_rollout_backward_ex(const aline_model *m, const aline_rollout *r, const float *g_logp,

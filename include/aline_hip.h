@@ -204,6 +204,12 @@ int aline_backward_recompute_name(const aline_model *m, const aline_rollout *r, 
  * "gemm_tn_block_kernel" (exact fp32), "gemm_tn_f16_kernel" (256 x 256 blocks) or "gemm_tn_f16_narrow_kernel<128, 128>" (a dimension a multiple of 128 only);
  * returns 1 for an f16 kernel, 0 for the fp32 one; negative on error.  Host logic only. */
 int aline_backward_dw_kernel_name(const aline_model *m, int N, int K, char *buf, size_t n);
+/* the attention-backward kernel of a training backward of m for a chunk whose instances have N token rows and at most max_keys visible
+ * keys, given the attention output and the scale word of dA as the backward has them: "abw16::attention_bwd16_kernel",
+ * "abw8::attention_bwd8_kernel", "abww::attention_bwd_wide_kernel" / "abww::attention_bwd_wide16_kernel", "abwl::attention_bwd_long_kernel",
+ * "abwl64::attention_bwd_long64_kernel", "abwd::attention_bwd_mfma_kernel", "attention_bwd_kernel" (fp32 VALU), or "unsupported" where
+ * no kernel's LDS holds the shape; returns >= 0, negative on error.  Host logic only. */
+int aline_backward_attn_kernel_name(const aline_model *m, int max_keys, int N, char *buf, size_t n);
 /* Task.update_batch equivalent for callers that want the reference layout back
  * (tasks/base_task.py:133-154): context_x/y [B,n_ctx0+T,*] in order of entry, query remainder. */
 int aline_rollout_export(const aline_rollout *r, int n_ctx, float *context_x, float *context_y,

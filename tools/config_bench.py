@@ -9,6 +9,8 @@ pairs of the x3 path and the generic pipeline (ALINE_DISABLE_X3) in one process,
 x1 path (ALINE_DISABLE_X1).
 --configs 1wt [--pairs N]: the training leg of 1w -- `train_step` at that geometry, N alternating pairs of the default backward
 (forward recompute on x1::layer_save_kernel) and ALINE_DBG_NO_BWD_IMAGE_RECOMPUTE (the generic recompute); --pairs 0: the default alone.
+--configs 2h16t,3h16t --train-flag NO_BWD_ATTN_MFMA [--pairs N]: `train_step` of the models with heads of 16 channels (d=64/F=256/H=4) at the
+headline geometry and at cfg3's, default (abw16::attention_bwd16_kernel) against the fp32 VALU attention backward.
 Random-init weights, synthetic task data, sampled designs, HIP-graph replay; which kernel path ran is reported."""
 import argparse
 import json
@@ -232,6 +234,16 @@ def main():
         batch = HiddenLocation(n_query_init=200, device=dev).sample_batch(1000)
         run_train_pairs("headline geometry at d=128 F=512 H=4 f16x3: location_finding B=1000 T=30, train_step",
                         build(2, 128, 512, 4, 2, "theta", "f16x3"), batch, 30, args.steps, args.pairs, args.train_flag)
+    if "2h16t" in want:   # heads of 16 channels: the headline geometry at d = 64 / F = 256 / H = 4, pairs against --train-flag NO_BWD_ATTN_MFMA
+        batch = HiddenLocation(n_query_init=200, device=dev).sample_batch(1000)
+        run_train_pairs("headline geometry at d=64 F=256 H=4 f16x3: location_finding B=1000 T=30, train_step",
+                        build(2, 64, 256, 4, 2, "theta", "f16x3"), batch, 30, args.steps, args.pairs, args.train_flag)
+    if "3h16t" in want:   # cfg3's geometry at d = 64 / F = 256 / H = 4 (up to 153 keys)
+        batch = GPTask(dim_x=2, embedding_type="mix", n_context_init=1, n_query_init=200, n_target_theta=3,
+                       n_target_data=100, device=dev).sample_batch(512)
+        batch["target_mask"] = create_target_mask("split", "mix", 100, 3, None, None, None, None, "data")
+        run_train_pairs("cfg3 geometry at d=64 F=256 H=4 f16x3: al_mix dx=2 B=512 T=50, split mask (data), train_step",
+                        build(2, 64, 256, 4, 3, "mix", "f16x3"), batch, 50, args.steps, args.pairs, args.train_flag)
     if "5t" in want:      # the training leg of cfg5 at F = 128 (its 128-wide weight-gradient products), pairs against --train-flag
         batch = PsychometricTask(n_query_init=200, n_context_init=1, device=dev).sample_batch(256)
         batch["target_mask"] = torch.tensor([False, False, True, True])
